@@ -14,8 +14,8 @@ is complete and the posterior fields are on rank 0 (one gather).  Measured on
 one MI355X (profiles/r02/): ordered/depth 1 57.1, ordered/depth 3 59.0,
 lpt/depth 3 58.0 cells/s; one whole-day oi_gpr_batch call 61.6 (round 1).  So `--steps K` times exactly the whole day once,
 whatever K; total work is fixed as N grows ("scaling": "strong").  `--warmup W`
-runs W untimed slices of 24 separate small cells (n ~ U{300..1200}) through the
-same session first.
+runs W of the timed slices (slice w mod K) untimed through the same session
+first and drains them, so a warmup step costs what a timed step costs.
 
 Other workloads: `days` (weak scaling: every rank fits its own synthetic day,
 seed + rank, in `--steps` slices), `predict` (config 2: 1000 cells x n = 500,
@@ -27,11 +27,21 @@ Inputs are resident in HBM before the timed region (device-input C-ABI path).
 The timed region is bracketed by barrier + device synchronise on every rank and
 the max over ranks is reported.  `--budget-s` (default 420 s of wall clock
 from process start) stops submitting slices early rather than being killed: the
-line then says `"truncated": true` with the slices actually timed.  The CPU
-baseline runs after the GPU leg (rank 0, N = 1) inside the remaining budget.
+line then says `"truncated": true` with the slices actually timed.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
-                       [--workload day|days|season|predict|single|nystrom|svgp]
+A plain run sets up, warms up, times the steps, writes `--dump-outputs DIR` if
+asked (what the last timed step returned to its caller, and the posterior
+fields of all timed steps on rank 0, as DIR/<name>.npy in float64; non-finite
+entries go to DIR/<name>_nonfinite.npy as indices, dump_outputs) and prints
+the line; the per-launch HIP events of day / days / season are inside the
+timed region, so their roofline is part of a plain line.  `--full` adds what
+takes runs of its own after the GPU leg: the CPU baseline (rank 0, N = 1,
+inside the remaining budget; `--no-cpu-baseline` drops it), the parity check
+of the timed cells against the CPU oracle (`--parity-cells`), and the
+profiled second pass behind the roofline of single / predict.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                       [--workload day|days|season|predict|single|nystrom|svgp|twopass]
 Multi-GPU: `python bench.py --gpus N` starts N rank processes itself (one per
 GPU, torch.distributed over RCCL; launch_ranks below) before anything touches
 the GPU, or run it under `python -m torch.distributed.run --nproc-per-node N
@@ -114,6 +124,15 @@ def parse():
     p.add_argument('--twopass-small', action='store_true',
                    help='twopass workload: a small binned day (48 x 48 grid, ~100 cells) -- tests / rehearsals only')
     p.add_argument('--dump', default='', help='write per-cell n, m, evals, status of the timed cells (.npz)')
+    p.add_argument('--full', action='store_true',
+                   help='after the timed steps also run everything beside the headline figure: the CPU baseline '
+                        '(unless --no-cpu-baseline), the parity check of the timed cells against the CPU oracle '
+                        '(--parity-cells), and the profiled second pass behind the roofline of single / predict. '
+                        'A plain run sets up, warms up, times the steps and prints the line')
+    p.add_argument('--dump-outputs', default='', metavar='DIR',
+                   help='after the timed steps write what the last timed step returned to its caller as '
+                        'DIR/<name>.npy (float64, finite entries only; the flat indices of NaN / infinite ones as '
+                        'DIR/<name>_nonfinite.npy; at most 64 MB in all, a fixed seeded sample of a larger array)')
     p.add_argument('--out', default='')
     return p.parse_args()
 
@@ -124,6 +143,44 @@ def elapsed():
 
 def log(msg):
     print(f"[bench {elapsed():6.1f}s] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_OUTPUTS_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: ``arrays`` {name: array} as ``dirname/<name>.npy``,
+    float32 kept, everything else (integer status / counters included) as
+    float64.  The files hold finite numbers only, so that two builds' files
+    can be compared number by number: an array with NaN or infinite entries --
+    a cell whose optimiser ran off to non-finite hypers (the line of search
+    the reference's scipy CG reports as "NaN result encountered"),
+    or the off-ice nodes of a day's grids -- is
+    written as its finite entries in flat order, and ``<name>_nonfinite.npy``
+    lists the flat indices of the others.  All files together hold at most
+    DUMP_OUTPUTS_MAX_BYTES: beyond that every array is cut to the same share
+    of its elements, a sample drawn once with a fixed seed (sorted flat
+    indices), so two runs with the same arguments write the same elements."""
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {}
+    for name, a in arrays.items():
+        if a is None:  # an output the call was not asked for
+            continue
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        fin = np.isfinite(a)
+        if not fin.all():
+            arrs[name + '_nonfinite'] = np.flatnonzero(~fin).astype(np.float64)
+            a = a[fin]
+        arrs[name] = a
+    total = sum(a.nbytes for a in arrs.values())
+    for name, a in arrs.items():
+        if total > DUMP_OUTPUTS_MAX_BYTES and a.size:
+            keep = max(1, int(a.size * (DUMP_OUTPUTS_MAX_BYTES / total) * 0.999))
+            idx = np.sort(np.random.default_rng(20261).choice(a.size, size=keep, replace=False))
+            a = a.ravel()[idx]
+        np.save(os.path.join(dirname, name + '.npy'), a)
+    log(f"--dump-outputs: {sorted(arrs)} -> {dirname}")
 
 
 # ----------------------------------------------------------------- host cores
@@ -236,8 +293,7 @@ def build_slices(args, rank, world):
     """-> (timed slices of this rank, warmup slices, opt, config, scaling,
     cells per rank of every rank)."""
     from optimalinterpolation_amd import driver, synthetic
-    warm = [synthetic.make_cells(np.random.default_rng(900 + g).integers(300, 1201, 24),
-                                 seed=1000 + 97 * g + rank) for g in range(args.warmup)]
+    warm = None  # day / days / season: a warmup step runs a timed step's own slice (main)
     if args.workload == 'season':
         # config 5: rank r fits share r of each of --season-days consecutive
         # season days (seed + d), the days one after another through one
@@ -634,7 +690,9 @@ def main_nystrom(args, torch, dist, world, rank, gpu, cdev):
                                       f", one batch per step through a fit session (depth {args.depth})"),
                        "cells_per_step": ncell * world},
             "evals_per_cell": round(float(np.mean(evals)), 2), "roofline": roofline, **args.dist_fields}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(('out', 'status', 'info'), outs[-1])))
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cores = host_cores(args)[0]
         try:
             line["cpu_baseline"] = nystrom_cpu_baseline(evals, cores)
@@ -758,7 +816,9 @@ def main_svgp(args, torch, dist, world, rank, gpu, cdev):
                                    f"M={SVGP_M}, B={SVGP_B}, {iters} Adam steps per rank per step",
                        "cells_per_step": k * world},
             "failed_cells": bad, "roofline": roofline, **args.dist_fields}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(('pred', 'status', 'params', 'elbo'), outs[-1])))
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cores = host_cores(args)[0]
         try:
             line["cpu_baseline"] = svgp_cpu_baseline(iters, cores)
@@ -820,7 +880,6 @@ def main_twopass(args, torch, dist, world, rank, gpu, cdev):
     production output `_interp_smth` -- as day.interpolate_day on a binned
     synthetic 25 km day (synthetic.make_binned_day: ~1e4 ice cells, ~300-3000
     observations within 300 km).  A step is one whole day (seed + step)."""
-    import tempfile
     from optimalinterpolation_amd import _lib, day as DAY, synthetic
     small = dict(nx=48, ice_radius_m=200e3, obs_radius_m=500e3, cover=(0.02, 0.06)) if args.twopass_small else {}
     days = [synthetic.make_binned_day(seed=args.seed + k, **small) for k in range(args.steps)]
@@ -887,7 +946,35 @@ def main_twopass(args, torch, dist, world, rank, gpu, cdev):
             "pass2_cells_per_s": round(ncell / max(tim['pass2_s'], 1e-12), 1),
             "evals_per_cell": round(float(np.mean(evals[ok])), 2), "failed_cells": int(np.sum(~ok)),
             "roofline": rl, **args.dist_fields}
-    # parity: smoothing bit-exact on the GPU's own pass-1 fields; pass 2 of sampled cells at T1
+    if args.dump_outputs:  # the last day's fields, the date prefix dropped so the names do not depend on it
+        last, dl = res[-1], days[-1]
+        dump_outputs(args.dump_outputs, {k[len(dl.date) + 1:] if k.startswith(dl.date + '_') else k: v
+                                         for k, v in last.items()})
+    if args.full:
+        line["parity"] = twopass_parity(args, r0, d0, ids, counts)
+    if world == 1 and args.full and not args.no_cpu_baseline:
+        workers, desc = host_cores(args)
+        try:
+            line["cpu_baseline"] = cpu_baseline(counts[ok], evals[ok], workers, desc, time.time() + 400,
+                                                extra_pred=1)
+        except Exception as e:
+            line["cpu_baseline"] = {"value": None, "error": repr(e)}
+    else:
+        line["cpu_baseline"] = None
+    s = json.dumps(line)
+    print(s, flush=True)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(s + '\n')
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def twopass_parity(args, r0, d0, ids, counts):
+    """--full, twopass workload: smoothing bit-exact on the GPU's own pass-1
+    fields; pass 2 of sampled cells at T1."""
+    import tempfile
+    from optimalinterpolation_amd import day as DAY, synthetic
     tmp = tempfile.mkdtemp(prefix='oi_twopass_')
     path = os.path.join(tmp, 'day.npz')
     p1 = np.stack([r0[d0.date + '_' + k] for k in DAY.HYPER_KEYS])
@@ -913,23 +1000,7 @@ def main_twopass(args, torch, dist, world, rank, gpu, cdev):
                    "smoothed fields (bitwise), and the oracle's GPR3D(opt=False) with the reference's cKDTree "
                    "neighbour order at the GPU's smoothed hypers vs the GPU's pass-2 fs / sd on a stratified "
                    "sample of cells (T1)")
-    line["parity"] = par
-    if world == 1 and not args.no_cpu_baseline:
-        workers, desc = host_cores(args)
-        try:
-            line["cpu_baseline"] = cpu_baseline(counts[ok], evals[ok], workers, desc, time.time() + 400,
-                                                extra_pred=1)
-        except Exception as e:
-            line["cpu_baseline"] = {"value": None, "error": repr(e)}
-    else:
-        line["cpu_baseline"] = None
-    s = json.dumps(line)
-    print(s, flush=True)
-    if args.out:
-        with open(args.out, 'w') as f:
-            f.write(s + '\n')
-    if world > 1:
-        dist.destroy_process_group()
+    return par
 
 
 # ----------------------------------------------------------------- launcher
@@ -1235,7 +1306,10 @@ def main():
         return (cells, torch.from_numpy(cells.xyt).to(dev).contiguous(),
                 torch.from_numpy(cells.z).to(dev).contiguous(), h)
     dev_slices = [resident(c) for c in slices]
-    dev_warm = [resident(c) for c in warm]
+    # a warmup step costs what a timed step costs: warmup step w of day / days / season is slice
+    # w mod K of the timed slices, submitted the same way and drained before the timed region
+    warm_k = [w % len(slices) for w in range(args.warmup)] if warm is None and slices else []
+    dev_warm = [resident(c) for c in warm or []]
     torch.cuda.synchronize()
 
     def submit(sess, item):
@@ -1279,6 +1353,8 @@ def main():
     else:
         for item in dev_warm:
             submit(sess, item)
+        for k in warm_k:
+            submit_queried(sess, k) if pool is not None else submit(sess, dev_slices[k])
         sess.wait(-1)
         if pool is not None:  # the query / gather code paths, untimed
             _lib.gather_rows_device(pool['cols'], _lib.ball_query_device(pool['pts'], pool['q'][0], pool['r'])[1])
@@ -1348,13 +1424,21 @@ def main():
     total_cells = float(tot.item())
     log(f"GPU leg: {total_cells:.0f} cells in {dt:.2f} s = {total_cells / dt:.3f} cells/s")
 
-    if single:  # the roofline's per-launch times: the same calls again, profiled, untimed
+    if args.dump_outputs and rank == 0 and done_k:
+        # the last timed step as its caller received it (sess.wait / gpr_batch_device), and the
+        # posterior fields of every timed step as the timed region leaves them on rank 0
+        fields = rows if world == 1 else np.concatenate([bufs[r][:int(cs[r].item())].cpu().numpy()
+                                                         for r in range(world)])
+        dump_outputs(args.dump_outputs, {**dict(zip(('out', 'status', 'info'), outs[done_k - 1])),
+                                         'fields': fields})
+    have_prof = tprof or args.full  # otherwise no launch of the timed cells was profiled: no roofline
+    if args.full and single:  # the roofline's per-launch times: the same calls again, profiled, untimed
         _lib.profile_reset()
         for k in range(done_k):
             cells, xyt, z, h = dev_slices[k]
             _lib.gpr_batch_device(xyt, z, cells.offs, cells.xs, cells.mean, x0=X0, opt=True, device=gpu,
                                   profile=True)
-    elif not tprof:  # the same slices again through a profiled session, untimed
+    elif args.full and not tprof:  # the same slices again through a profiled session, untimed
         _lib.profile_reset()
         psess = _lib.Session(device=gpu, device_inputs=True, profile=True, max_pool=args.max_pool)
         for k in range(done_k):
@@ -1378,12 +1462,13 @@ def main():
             "data": "synthetic (seeded SURVEY §8d generator; reference data not shipped)",
             "config": cfg, "evals_per_cell": round(float(np.mean(evals)), 2) if opt else 0,
             "failed_cells": int(np.sum(status != 0)), "timed_s": round(dt, 3),
-            "roofline": roofline_of(prof, evals, n, dt, sizes_timed.astype(float)), **args.dist_fields}
+            "roofline": roofline_of(prof, evals, n, dt, sizes_timed.astype(float)) if have_prof else None,
+            **args.dist_fields}
     line["per_rank"] = [{"rank": int(r), "cells": int(c), "own_work_s": round(t, 3), "evals": int(e),
                          "tail_round_gpu_ms": (round(m, 1) if m >= 0 else None)} for r, c, t, e, m in per_rank]
     if world > 1:
         line["config"]["cells_per_rank"] = [int(c) for c in counts_all]
-    if not tprof:
+    if have_prof and not tprof:
         line["roofline"]["timing_note"] = ("per-launch HIP-event times from a second, profiled pass over the "
                                            "same cells; the timed pass runs without per-launch events")
     rl = prof.get('rounds_log') or []
@@ -1394,14 +1479,15 @@ def main():
         line["rounds"] = {"count": len(rl), "gpu_ms": round(tot, 1),
                           "lt256_cells": len(small), "lt256_gpu_ms": round(sum(r[4] for r in small), 1),
                           "note": "rounds with < 256 resident cells (the day's tail of slow-converging cells)"}
-    dom = line["roofline"]["kernel"]
-    pu, pt = prof_untimed.get(dom, {"launches": 0, "total_ms": 0.0}), prof["kernels"][dom]
-    nall = pu["launches"] + pt["launches"]
-    line["roofline"]["rocprof_crosscheck"] = {
-        "launches_incl_untimed": nall,
-        "avg_launch_ms_incl_untimed": (pu["total_ms"] + pt["total_ms"]) / max(nall, 1),
-        "note": "HIP-event average over every launch of the process (priming + warmup + timed), the set a "
-                "rocprofv3 --kernel-trace --stats run of this command averages over"}
+    if have_prof:
+        dom = line["roofline"]["kernel"]
+        pu, pt = prof_untimed.get(dom, {"launches": 0, "total_ms": 0.0}), prof["kernels"][dom]
+        nall = pu["launches"] + pt["launches"]
+        line["roofline"]["rocprof_crosscheck"] = {
+            "launches_incl_untimed": nall,
+            "avg_launch_ms_incl_untimed": (pu["total_ms"] + pt["total_ms"]) / max(nall, 1),
+            "note": "HIP-event average over every launch of the process (priming + warmup + timed), the set a "
+                    "rocprofv3 --kernel-trace --stats run of this command averages over"}
     if done_k != args.steps or truncated:
         line.update({"truncated": True, "steps_requested": args.steps})
     if args.dump and rank == 0:  # per (kernel, block column) launch totals of the profiled pass
@@ -1410,9 +1496,9 @@ def main():
     if args.dump:
         np.savez(args.dump if rank == 0 else f"{args.dump}.rank{rank}.npz", n=sizes_timed, m=sites_timed,
                  evals=info[:, 3], nit=info[:, 0], cg_status=info[:, 1], status=status)
-    if rank == 0:
+    if rank == 0 and args.full:
         log("line (before cpu_baseline): " + json.dumps({k: line[k] for k in ('value', 'steps', 'ms_per_step')}))
-    if rank == 0 and opt and args.parity_cells > 0 and args.workload in ('day', 'days', 'season'):
+    if rank == 0 and args.full and opt and args.parity_cells > 0 and args.workload in ('day', 'days', 'season'):
         try:
             timed = [slices[k] for k in range(done_k)]
             rows = np.concatenate([outs[k][0] for k in range(done_k)])
@@ -1420,7 +1506,8 @@ def main():
                                           T_PROC + args.budget_s + 10.0, host_cores(args)[0])
         except Exception as e:  # never lose the GPU line over the check
             line["parity"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and opt and args.workload != 'single':
+    cpu = rank == 0 and world == 1 and args.full and not args.no_cpu_baseline
+    if cpu and opt and args.workload != 'single':
         workers, desc = host_cores(args)
         if args.workload == 'season':
             global EVAL_PROBES
@@ -1433,10 +1520,10 @@ def main():
                 line["cpu_baseline"] = cpu_baseline(sizes_timed, evals, workers, desc, deadline)
             except Exception as e:  # never lose the GPU line over the baseline
                 line["cpu_baseline"] = {"value": None, "error": repr(e)}
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline and not opt:
+    elif cpu and not opt:
         workers, desc = host_cores(args)
         line["cpu_baseline"] = cpu_predict_baseline(workers, desc)
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline and single:
+    elif cpu and single:
         workers, desc = host_cores(args)
         line["cpu_baseline"] = cpu_single_baseline([args.seed + 31 * k for k in range(done_k)], workers, desc)
     else:

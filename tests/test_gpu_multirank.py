@@ -130,7 +130,7 @@ def test_bench_self_launch_gloo(tmp_path):
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT'):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '4',
-                        '--warmup', '1', '--day-cells', '96', '--no-cpu-baseline', '--parity-cells', '4',
+                        '--warmup', '1', '--day-cells', '96', '--full', '--no-cpu-baseline', '--parity-cells', '4',
                         '--budget-s', '90', '--out', str(out)],
                        env=env, capture_output=True, text=True, timeout=110)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -165,8 +165,8 @@ def test_bench_under_torchrun_gloo(tmp_path):
     p = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
                         '--master-addr', '127.0.0.1', '--master-port', str(_free_port()),
                         os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1',
-                        '--day-cells', '96', '--no-cpu-baseline', '--parity-cells', '4', '--budget-s', '90',
-                        '--out', str(out)],
+                        '--day-cells', '96', '--full', '--no-cpu-baseline', '--parity-cells', '4',
+                        '--budget-s', '90', '--out', str(out)],
                        env=env, capture_output=True, text=True, timeout=110, cwd=root)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads(out.read_text())
@@ -188,7 +188,7 @@ def test_bench_twopass_small(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = tmp_path / 'twopass.json'
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--workload', 'twopass', '--twopass-small',
-                        '--steps', '1', '--no-cpu-baseline', '--parity-cells', '6', '--out', str(out)],
+                        '--steps', '1', '--full', '--no-cpu-baseline', '--parity-cells', '6', '--out', str(out)],
                        capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads(out.read_text())
