@@ -24,7 +24,9 @@ struct LinalgErr {  // thrown by the host routines on a HIP error or an operand 
 // C = alpha op(A) op(B) + beta C  (m x n, inner dimension k); tri:
 //   0  all output tiles;
 //   1  lower output tiles only (64-tile row >= 64-tile column; syrk-like);
-//   2  op(B) upper triangular: output column tile jt only sums k < 64 (jt + 1)
+//   2  op(B) upper triangular: output column tile jt only sums k < 64 (jt + 1);
+//   3  as 1, and inside the diagonal tiles only the entries with row >= column
+//      (the strict upper triangle of C is neither read nor written)
 struct Gemm {
   const double* A;
   const double* B;
@@ -48,7 +50,9 @@ struct Gemv {
 // ascending), its workspace (workspace_doubles(M) doubles), and info (device,
 // may be null): set to 1 -- LAPACK syevd's info > 0, numpy's LinAlgError --
 // when the orthogonalisation cannot produce a finite column in its four
-// attempts; left untouched otherwise (NaN input propagates as NaN).
+// attempts; left untouched otherwise (NaN input propagates as NaN, into w too).
+// Any spectrum: clusters of numerically equal eigenvalues anywhere in it get an
+// eigenbasis (inverse iteration inside the cluster, as LAPACK's dstein).
 struct Eigh {
   double* A;
   double* w;
@@ -59,7 +63,7 @@ struct Eigh {
 size_t eigh_workspace_doubles(int M);
 
 // One SPD matrix for the blocked Cholesky: A (M x M, lower triangle; the
-// factor L overwrites it), dinv (ceil(M/64) x 4096 doubles: the inverses of
+// factor L overwrites it; the strict upper triangle is left untouched), dinv (ceil(M/64) x 4096 doubles: the inverses of
 // L's 64 x 64 diagonal blocks, kept for trsm_right_lt), info (0, or 1 when
 // a pivot is <= 0, as LAPACK dpotrf's info > 0; a NaN pivot propagates, as
 // numpy + OpenBLAS's dpotrf let it).

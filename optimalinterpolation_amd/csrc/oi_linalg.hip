@@ -30,8 +30,9 @@
 //                 them into Z
 //   k_orth_panel  Cholesky QR twice inside a 32-vector panel (Gram-Schmidt
 //                 in column order; G = Z'Z on MFMA); where a column
-//                 collapses (repeated eigenvalues) classical Gram-Schmidt
-//                 twice column by column with fresh start vectors
+//                 keeps little of its norm (repeated eigenvalues) classical
+//                 Gram-Schmidt twice column by column, a collapsed column
+//                 replaced through inverse iteration as in dstein
 //                 (k_mgs_panel); between panels block Gram-Schmidt twice
 //                 (BCGS2) on k_gemm
 //   back-transform U = Q Z, one block reflector I - V T V' per panel (k_gemm)
@@ -111,7 +112,7 @@ __global__ __launch_bounds__(256) void k_gemm(const Gemm* __restrict__ gs) {
   const int tm = (g.m + GT - 1) / GT, tn = (g.n + GT - 1) / GT;
   if ((int)blockIdx.x >= tm * tn) return;
   const int it = blockIdx.x % tm, jt = blockIdx.x / tm;
-  if (g.tri == 1 && it < jt) return;
+  if ((g.tri == 1 || g.tri == 3) && it < jt) return;
   int kmax = g.k;
   if (g.tri == 2) kmax = min(kmax, GT * (jt + 1));
   const int m0 = GT * it, n0 = GT * jt;
@@ -206,6 +207,7 @@ __global__ __launch_bounds__(256) void k_gemm(const Gemm* __restrict__ gs) {
   for (int e = t; e < GT * GT; e += 256) {
     const int m = e & 63, n = e >> 6, gm = m0 + m, gn = n0 + n;
     if (gm >= g.m || gn >= g.n) continue;
+    if (g.tri == 3 && gm < gn) continue;  // the strict upper triangle stays as it is
     gdouble* c = G(g.C) + gm + (size_t)g.ldc * gn;
     const double v = g.alpha * X[n * 65 + m];
     *c = g.beta == 0.0 ? v : v + g.beta * *c;
@@ -464,7 +466,7 @@ __host__ __device__ inline EighWs carve(double* w, int M) {
   s.d = s.T + ((size_t)(M + TNB - 1) / TNB + 1) * TNB * TNB;
   s.e = s.d + M + 1;
   s.tau = s.e + M + 1;
-  s.flag = s.tau + M + 1;  // k_orth_panel -> k_mgs_panel: the panel collapsed
+  s.flag = s.tau + M + 1;  // [0] k_orth_panel -> k_mgs_panel: 1 the panel is handed over, 2 weak columns [3]; [1] nb0, [2] ||T|| (k_stein)
   return s;
 }
 struct EighWsG {  // carve() as global-address-space pointers (device side)
@@ -778,12 +780,15 @@ __device__ __forceinline__ void tri_setup(const Eigh& E, const EighWsG& ws, doub
   __syncthreads();
   if (t == 0) {  // Gershgorin interval, ||T||, pivmin (dstebz)
     double gl = d[0], gu = d[0], emax2 = 0.0;
+    bool nan = false;  // fmin / fmax drop a NaN operand: NaN input must reach the eigenvalues
     for (int i = 0; i < M; ++i) {
       const double ae = (i > 0 ? fabs(ws.e[i - 1]) : 0.0) + (i < M - 1 ? fabs(ws.e[i]) : 0.0);
+      nan = nan || !(d[i] == d[i]) || !(ae == ae);
       gl = fmin(gl, d[i] - ae);
       gu = fmax(gu, d[i] + ae);
       emax2 = fmax(emax2, e2[i]);
     }
+    if (nan) gl = gu = __builtin_nan("");
     const double tnorm = fmax(fabs(gl), fabs(gu));
     const double eps = 2.220446049250313e-16, pivmin = 2.2250738585072014e-308 * fmax(1.0, emax2);
     red[0] = gl - 2.1 * tnorm * eps * M - 2.1 * pivmin;
@@ -809,6 +814,10 @@ __global__ __launch_bounds__(ST_T) void k_stebz(const Eigh* __restrict__ es) {
   {
     const int k = (int)blockIdx.y * ST_T + t;
     if (k >= M) return;
+    if (!(GL == GL)) {  // NaN in the tridiagonal: NaN eigenvalues, as numpy's eigh
+      G(E.w)[k] = GL;
+      return;
+    }
     // eigenvalue k (ascending): count(x) = #eigenvalues < x; lambda_k = sup{x : count(x) <= k}
     // (bisection; multisection with 2 / 4 / 8 interleaved Sturm counts per
     // sweep, also with v_rcp_f64 + Newton in place of the division, measured
@@ -874,6 +883,10 @@ __global__ __launch_bounds__(ST_T) void k_stein(const Eigh* __restrict__ es) {
     int nb0 = 1;
     while (nb0 < M && w[nb0] - w[nb0 - 1] <= gtol) ++nb0;
     red[4] = nb0 >= 2 ? (double)nb0 : 0.0;
+    if (blockIdx.y == 0) {  // for k_mgs_panel
+      ws.flag[1] = red[4];
+      ws.flag[2] = tnorm;
+    }
   }
   __syncthreads();
   const int nb0 = (int)red[4];
@@ -935,7 +948,7 @@ __global__ __launch_bounds__(ST_T) void k_stein(const Eigh* __restrict__ es) {
       sp[o] = 0.0;
     }
     for (int i = 0; i < M; ++i) sx[(size_t)i * M + k] = start_value(k, i);
-    const double tol = eps * tnorm;
+    const double tol = fmax(eps * tnorm, 2.2250738585072014e-308);  // T == 0: no division by zero
     for (int iter = 0; iter < 2; ++iter) {
       // forward: apply P and L
       double prev = sx[k];
@@ -1015,19 +1028,40 @@ __global__ __launch_bounds__(256) void k_reverse_cols(const Eigh* __restrict__ e
 }
 
 // ------------------------------------------------------------ k_mgs_panel
-// Columns [p, q) of Z (already orthogonal to columns < p): classical
-// Gram-Schmidt twice against the panel's earlier columns, normalise; a column
-// that collapses (repeated eigenvalue) is replaced by a fresh start vector
-// projected out of every earlier column.
+// Columns [p, q) of Z (orthogonal to columns < p up to rounding): classical
+// Gram-Schmidt twice against the panel's earlier columns, normalise.  A column
+// that keeps no more than MG_WEAK of its squared norm is weak (normalising it
+// magnifies what rounding left in it of other eigenvectors by 1 / sqrt of the
+// fraction kept); one that keeps no more than MG_COLLAPSE has collapsed
+// (numerically repeated eigenvalue: inverse iteration gave a vector in the
+// span of the earlier ones).
+//   In the bottom cluster (k_stein's random starts: eigenvalue index < nb0,
+// the last columns) the complement of every earlier column IS the eigenspace:
+// a weak column is projected out of EVERY earlier column before it is
+// normalised, a collapsed one replaced by a fresh start vector treated alike.
+//   Anywhere else such a vector lies in the span of ALL remaining eigenvectors
+// -- an orthonormal basis that is no eigenbasis -- so a weak or collapsed
+// column is replaced as LAPACK's dstein does inside a cluster: a fresh start
+// vector, projected out of every earlier column, put through inverse
+// iteration on T - lambda_j I (k_stein's dlagtf / dlagts steps, serial on one
+// thread: a rare path) and projected again, MG_ITERS times.
+// tools/eigh_model.py: mgs.
 #define MG_T 256
+#define MG_WEAK 1e-2
+#define MG_COLLAPSE 1e-4
+#define MG_ITERS 3
 __global__ __launch_bounds__(MG_T) void k_mgs_panel(const Eigh* __restrict__ es, int p) {
   __shared__ double red[4 * 33];
   const Eigh E = es[blockIdx.x];
   const int M = E.M;
-  if (p >= M || carve(E.work, M).flag[0] == 0.0) return;  // k_orth_panel's Cholesky QR held
+  const double handed = p < M ? carve(E.work, M).flag[0] : 0.0;
+  if (handed == 0.0) return;  // k_orth_panel's Cholesky QR held
   const int q = min(M, p + TNB), t = threadIdx.x, lane = t & 63, w = t >> 6;
   gdouble* Z = G(E.A);
   const size_t ld = E.lda;
+  const EighWsG ws = carveG(E.work, M);
+  const int nb0 = (int)ws.flag[1];    // k_stein: size of the bottom cluster
+  const double tnorm = ws.flag[2];    // k_stein: ||T||
   auto reduce = [&](double (&v)[33]) {  // fixed-order sums of 33 values
 #pragma unroll
     for (int a = 0; a < 33; ++a)
@@ -1041,46 +1075,143 @@ __global__ __launch_bounds__(MG_T) void k_mgs_panel(const Eigh* __restrict__ es,
     for (int a = 0; a < 33; ++a) v[a] = ((red[a] + red[33 + a]) + red[66 + a]) + red[99 + a];
     __syncthreads();
   };
-  for (int j = p; j < q; ++j) {
-    gdouble* zj = Z + ld * j;
-    bool done = false, nan = false;
-    for (int attempt = 0; attempt < 4; ++attempt) {
-      const int lo = attempt == 0 ? p : 0;  // a fresh vector is projected out of everything
-      double dv[33];
+  auto norm2 = [&](const gdouble* zj) {
+    double dv[33];
 #pragma unroll
-      for (int a = 0; a < 33; ++a) dv[a] = 0.0;
-      for (int i = t; i < M; i += MG_T) dv[32] += zj[i] * zj[i];
-      reduce(dv);
-      const double n0 = dv[32];
-      for (int pass = 0; pass < 2; ++pass) {
-        for (int b0 = lo; b0 < j; b0 += 32) {
-          const int nb = min(32, j - b0);
+    for (int a = 0; a < 33; ++a) dv[a] = 0.0;
+    for (int i = t; i < M; i += MG_T) dv[32] += zj[i] * zj[i];
+    reduce(dv);
+    return dv[32];
+  };
+  auto project = [&](gdouble* zj, int lo, int j, int passes = 2) {  // zj -= Z(:, lo:j) Z(:, lo:j)' zj, twice
+    for (int pass = 0; pass < passes; ++pass) {
+      for (int b0 = lo; b0 < j; b0 += 32) {
+        const int nb = min(32, j - b0);
+        double dv[33];
 #pragma unroll
-          for (int a = 0; a < 33; ++a) dv[a] = 0.0;
-          for (int i = t; i < M; i += MG_T) {
-            const double x = zj[i];
+        for (int a = 0; a < 33; ++a) dv[a] = 0.0;
+        for (int i = t; i < M; i += MG_T) {
+          const double x = zj[i];
 #pragma unroll
-            for (int a = 0; a < 32; ++a)
-              if (a < nb) dv[a] += Z[ld * (b0 + a) + i] * x;
-          }
-          reduce(dv);
-          for (int i = t; i < M; i += MG_T) {
-            double x = zj[i];
+          for (int a = 0; a < 32; ++a)
+            if (a < nb) dv[a] += Z[ld * (b0 + a) + i] * x;
+        }
+        reduce(dv);
+        for (int i = t; i < M; i += MG_T) {
+          double x = zj[i];
 #pragma unroll
-            for (int a = 0; a < 32; ++a)
-              if (a < nb) x -= dv[a] * Z[ld * (b0 + a) + i];
-            zj[i] = x;
-          }
-          __syncthreads();
+          for (int a = 0; a < 32; ++a)
+            if (a < nb) x -= dv[a] * Z[ld * (b0 + a) + i];
+          zj[i] = x;
+        }
+        __syncthreads();
+      }
+    }
+  };
+  // T - lam I = P L U (dlagtf, as k_stein) into the stein scratch, which is
+  // free here (H of the block projections is dead between their launches)
+  gdouble* fa = ws.scr + (size_t)M * M;  // U diagonal
+  gdouble* fb = fa + M;                  // U first superdiagonal
+  gdouble* fc = fb + M;                  // U second superdiagonal
+  gdouble* fl = fc + M;                  // L multipliers
+  gdouble* fp = fl + M;                  // row interchange flags
+  auto factor = [&](double lam) {        // one thread
+    double ak = ws.d[0] - lam, bk = M > 1 ? ws.e[0] : 0.0;
+    for (int i = 0; i < M - 1; ++i) {
+      const double sub = ws.e[i];
+      const double an = ws.d[i + 1] - lam, bn = i + 1 < M - 1 ? ws.e[i + 1] : 0.0;
+      double m, cnew = 0.0, a_i, b_i, a_next, b_next, piv = 0.0;
+      if (fabs(ak) >= fabs(sub)) {
+        m = ak != 0.0 ? sub / ak : 0.0;
+        a_i = ak;
+        b_i = bk;
+        a_next = an - m * bk;
+        b_next = bn;
+      } else {
+        m = ak / sub;
+        piv = 1.0;
+        a_i = sub;
+        b_i = an;
+        a_next = bk - m * an;
+        if (i < M - 2) {
+          cnew = bn;
+          b_next = -m * cnew;
+        } else {
+          b_next = bn;
         }
       }
-#pragma unroll
-      for (int a = 0; a < 33; ++a) dv[a] = 0.0;
-      for (int i = t; i < M; i += MG_T) dv[32] += zj[i] * zj[i];
-      reduce(dv);
-      const double n1 = dv[32];
+      fa[i] = a_i;
+      fb[i] = b_i;
+      fc[i] = cnew;
+      fl[i] = m;
+      fp[i] = piv;
+      ak = a_next;
+      bk = b_next;
+    }
+    fa[M - 1] = ak;
+    fb[M - 1] = 0.0;
+    fc[M - 1] = 0.0;
+    fl[M - 1] = 0.0;
+    fp[M - 1] = 0.0;
+  };
+  auto solve = [&](gdouble* x) {  // one thread: x <- (T - lam I)^-1 x scaled to max |x_i| = 1 (dlagts, job = -1)
+    const double tol = fmax(2.220446049250313e-16 * tnorm, 2.2250738585072014e-308);
+    double prev = x[0];
+    for (int i = 0; i < M - 1; ++i) {
+      const double nx = x[i + 1];
+      if (fp[i] != 0.0) {
+        x[i] = nx;
+        prev = prev - fl[i] * nx;
+      } else {
+        x[i] = prev;
+        prev = nx - fl[i] * prev;
+      }
+    }
+    x[M - 1] = prev;
+    double x1 = 0.0, x2 = 0.0, amax = 0.0;
+    for (int i = M - 1; i >= 0; --i) {
+      const double s = x[i] - fb[i] * x1 - fc[i] * x2;
+      double a = fa[i];
+      if (fabs(a) < tol) a = a >= 0.0 ? tol : -tol;
+      const double xi = s / a;
+      x[i] = xi;
+      x2 = x1;
+      x1 = xi;
+      amax = fmax(amax, fabs(xi));
+    }
+    const double inv = 1.0 / amax;
+    for (int i = 0; i < M; ++i) x[i] *= inv;
+  };
+  if (handed == 2.0) {
+    // the Cholesky QR held; its weak columns of the bottom cluster (bit j - p of
+    // flag[3]) are orthonormal in the panel and within the magnified rounding
+    // of the earlier panels: one projection out of every earlier column
+    const unsigned weak = (unsigned)ws.flag[3];
+    for (int j = p; j < q; ++j) {
+      if (!((weak >> (j - p)) & 1u)) continue;
+      gdouble* zj = Z + ld * j;
+      project(zj, 0, j, 1);
+      const double inv = 1.0 / sqrt(norm2(zj));
+      for (int i = t; i < M; i += MG_T) zj[i] *= inv;
+      __syncthreads();
+    }
+    return;
+  }
+  for (int j = p; j < q; ++j) {
+    gdouble* zj = Z + ld * j;
+    const bool bottom = M - 1 - j < nb0;
+    const double keep = bottom ? MG_COLLAPSE : MG_WEAK;
+    bool done = false, nan = false;
+    for (int attempt = 0; attempt < 4; ++attempt) {
+      const double n0 = norm2(zj);
+      project(zj, attempt == 0 ? p : 0, j);  // a fresh vector is projected out of everything
+      double n1 = norm2(zj);
       nan = nan || !(n0 == n0) || !(n1 == n1);
-      if (n1 > 1e-4 * n0 && n1 > 0.0) {
+      if (n1 > keep * n0 && n1 > 0.0) {
+        if (attempt == 0 && p > 0 && !(n1 > MG_WEAK * n0)) {  // weak, bottom cluster
+          project(zj, 0, j);
+          n1 = norm2(zj);
+        }
         const double inv = 1.0 / sqrt(n1);
         for (int i = t; i < M; i += MG_T) zj[i] *= inv;
         __syncthreads();
@@ -1089,6 +1220,16 @@ __global__ __launch_bounds__(MG_T) void k_mgs_panel(const Eigh* __restrict__ es,
       }
       for (int i = t; i < M; i += MG_T) zj[i] = start_value(j + 7919 * (attempt + 1), i);
       __syncthreads();
+      if (!bottom) {
+        project(zj, 0, j);
+        if (t == 0) factor(G(E.w)[M - 1 - j]);
+        for (int it = 0; it < MG_ITERS; ++it) {
+          __syncthreads();
+          if (t == 0) solve(zj);
+          __syncthreads();
+          project(zj, 0, j);
+        }
+      }
     }
     // four collapses in a row of a finite column: it is not an orthonormal
     // vector (reported like a non-converged syevd).  NaN input
@@ -1101,9 +1242,10 @@ __global__ __launch_bounds__(MG_T) void k_mgs_panel(const Eigh* __restrict__ es,
 // Columns [p, q) of Z (already orthogonal to columns < p): Cholesky QR twice --
 // G = Z_p' Z_p on the MFMA core, G = R'R, Z_p <- Z_p R^-1 -- the same
 // Gram-Schmidt in column order as mgs_panel in 2 block reductions per pass
-// instead of 4 per column.  A pivot that keeps no more than 1e-4 of its
-// column's squared norm (mgs_panel's collapse rule: numerically repeated
-// eigenvalues) hands the panel to k_mgs_panel and its fresh start vectors.
+// instead of 4 per column.  A pivot that keeps no more than MG_COLLAPSE of its
+// column's squared norm, or no more than MG_WEAK above the bottom cluster
+// (mgs_panel's rules: numerically repeated eigenvalues), hands the panel to
+// k_mgs_panel; a weak column of the bottom cluster is only marked for it.
 #define RL (TNB + 1)  // LDS row stride of R and R^-1
 __global__ __launch_bounds__(MG_T) void k_orth_panel(const Eigh* __restrict__ es, int p) {
   __shared__ double Gw[MG_T / 64][TNB * TNB];
@@ -1111,15 +1253,20 @@ __global__ __launch_bounds__(MG_T) void k_orth_panel(const Eigh* __restrict__ es
   __shared__ double Ri[TNB * RL];
   __shared__ double gd[TNB];
   __shared__ int bad;
+  __shared__ unsigned weakm;
   const Eigh E = es[blockIdx.x];
   const int M = E.M;
   if (p >= M) return;
+  const int nb0 = (int)carve(E.work, M).flag[1];  // k_stein: size of the bottom cluster
   const int nb = min(TNB, M - p), t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int fr = lane & 15, fk = lane >> 4;
   const size_t ld = E.lda;
   gdouble* Z = G(E.A) + ld * p;
   const Rsrc rz = rsrc(E.A + ld * p);
-  if (t == 0) carve(E.work, M).flag[0] = 0.0;
+  if (t == 0) {
+    carve(E.work, M).flag[0] = 0.0;
+    weakm = 0u;
+  }
   for (int pass = 0; pass < 2; ++pass) {
     // (1) G = Z_p' Z_p: wave w sums the 16-row blocks 16 (w + 4 j), 4 k-steps per batch
     Quad acc;
@@ -1179,11 +1326,20 @@ __global__ __launch_bounds__(MG_T) void k_orth_panel(const Eigh* __restrict__ es
 #pragma unroll
       for (int k = 0; k < TNB; ++k) g[k] = c < TNB ? R[k + RL * c] : 0.0;
       bool badl = false;
+      unsigned weakl = 0u;
 #pragma unroll
       for (int j = 0; j < TNB; ++j) {
         if (j < nb) {  // uniform
           const double dj = __shfl(g[j], j, 64);
-          if (!(dj > 1e-4 * gd[j])) badl = true;
+          // collapsed: k_mgs_panel takes the panel; weak: the same above the
+          // bottom cluster (the column is replaced), inside it the panel is
+          // kept and k_mgs_panel projects the column once more (no earlier
+          // panel at p == 0: nothing to do)
+          if (!(dj > MG_COLLAPSE * gd[j])) badl = true;
+          else if (!(dj > MG_WEAK * gd[j])) {
+            if (!(M - 1 - (p + j) < nb0)) badl = true;
+            else if (p > 0) weakl |= 1u << j;
+          }
           const double rjj = sqrt(fmax(dj, 1e-300));
           const double inv = 1.0 / rjj;
           if (c == j) g[j] = rjj;
@@ -1198,7 +1354,10 @@ __global__ __launch_bounds__(MG_T) void k_orth_panel(const Eigh* __restrict__ es
       if (c < TNB)
 #pragma unroll
         for (int k = 0; k < TNB; ++k) R[k + RL * c] = g[k];
-      if (lane == 0) bad = badl;
+      if (lane == 0) {
+        bad = badl;
+        weakm |= weakl;
+      }
       // R^-1 (upper), lane l = column l: x_a = (delta_al - sum_{k>a} R(a,k) x_k) / R(a,a);
       // x_k = +0 for k > l and past nb, so the sums are the k <= l ones exactly
       if (!badl && c < TNB) {
@@ -1257,6 +1416,10 @@ __global__ __launch_bounds__(MG_T) void k_orth_panel(const Eigh* __restrict__ es
       for (int kk = 0; kk < TNB / 4; ++kk) za[kk] = zn[kk];
     }
     __syncthreads();
+  }
+  if (t == 0 && weakm) {  // k_mgs_panel projects the weak columns once more
+    carve(E.work, M).flag[3] = (double)weakm;
+    carve(E.work, M).flag[0] = 2.0;
   }
 }
 
@@ -1377,9 +1540,9 @@ void cholesky(Stager& S, hipStream_t st, const std::vector<Chol>& cs) {
       double* colj = c.A + (jb + 64) + (size_t)c.lda * jb;
       // L(jb+64:, jb) = A(jb+64:, jb) Dinv_jj^T (in place: each output tile reads only its own rows)
       pan.push_back(Gemm{colj, c.dinv + (size_t)(jb / 64) * 4096, colj, rest, 64, 64, c.lda, 64, c.lda, 1.0, 0.0, 0});
-      // A(jb+64:, jb+64:) -= L L^T, lower tiles
+      // A(jb+64:, jb+64:) -= L L^T, lower triangle only (A's strict upper triangle is left alone)
       upd.push_back(Gemm{colj, colj, c.A + (jb + 64) + (size_t)c.lda * (jb + 64), rest, rest, 64, c.lda, c.lda,
-                         c.lda, -1.0, 1.0, 1});
+                         c.lda, -1.0, 1.0, 3});
     }
     gemm(S, st, false, true, pan);
     gemm(S, st, false, true, upd);
