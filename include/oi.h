@@ -8,6 +8,9 @@
  *                       GPR3D(index, opt=False)): one call fits / predicts a
  *                       ragged batch of cells.  Per cell it computes exactly
  *                       what GPR3D (GPR:143-191) returns.
+ *   oi_gpr_predict_multi  the predict step (GPR:173-182) at many targets per
+ *                       cell, as GP_example.ipynb's GPR() takes them (xs of
+ *                       size ns x 3), with the full posterior covariance.
  *   oi_nlml_grad_batch  replaces SMLII (GPR:107-141) for a batch of cells at
  *                       given log-hyper-parameters.
  *   oi_cg_*             the host optimiser on its own: scipy's
@@ -80,6 +83,33 @@ int oi_gpr_batch(const double* xyt, const double* z, const int64_t* offs, int64_
  * first waits for the legacy NULL stream (PyTorch's default stream), so any
  * producer of xyt / z / y / mX queued there has finished.  A producer on
  * another stream must pass that stream.  Host outputs are complete on return. */
+
+/* Prediction at many targets per cell, with the posterior covariance: the
+ * notebook's GPR(x, y, xs, ell, sf2, sn2, mean) (GP_example.ipynb, code cell 1)
+ * with xs of size ns x 3 -- GPR3D's predict step (GPR:173-182) with ns columns
+ * -- for a ragged batch at given hypers (as the opt == 0 call above).
+ *   xyt, z, offs, mean  as above (device pointers with opts->device_inputs)
+ *   xs     [T x 3]  targets of all cells, cell c owning rows
+ *                   toffs[c] .. toffs[c+1]-1; no target (nt = 0) is valid
+ *   toffs  [ncell+1] target offsets, toffs[0] = 0, non-decreasing
+ *   hyp    [ncell x 5] LINEAR (lx, ly, lt, sf2, sn2)
+ *   fs     [T]      mean + Kxsx' A                              (GPR:180)
+ *   sd     [T]      sqrt(diag(Kxs - v'v)); NaN where the argument is
+ *                   negative, as np.sqrt                        (GPR:181)
+ *   lz     [ncell] or NULL: the log marginal likelihood         (GPR:179)
+ *   cov    or NULL: Kxs - v'v in full (GPR:181 before its diagonal is taken),
+ *                   cell c's nt x nt matrix symmetric, row-major, at offset
+ *                   sum_{k<c} nt_k^2; the diagonal of Kxs is sf2 exactly
+ *   status [ncell]  0 ok, 1 covariance not positive definite: that cell's fs,
+ *                   sd, lz and cov are NaN (GPR:187-191)
+ * A cell with no observations gives fs = mean, sd = sqrt(sf2), lz = -0,
+ * cov = Kxs.  Cells are worked in chunks that fit opts->pool_bytes (0 => 60%
+ * of the free HBM); a cell that does not fit alone is OI_E_NOMEM.  A cell's
+ * results do not depend on the other cells of the call or on the chunking. */
+int oi_gpr_predict_multi(const double* xyt, const double* z, const int64_t* offs, int64_t ncell,
+                         const double* xs, const int64_t* toffs, double mean, const double* hyp,
+                         double* fs, double* sd, double* lz, double* cov,
+                         int32_t* status, const oi_options* opts);
 
 /* ---- session: continuous batching across calls ------------------------
  * The per-cell loops GPR:258-261 / GPR:316-319 as a stream of batches: every

@@ -38,7 +38,7 @@ EXPORTS = ('oi_options_default', 'oi_gpr_batch', 'oi_nlml_grad_batch', 'oi_cg_cr
            'oi_nystrom_fit_batch', 'oi_svgp_batch', 'oi_svgp_param_count', 'oi_session_create',
            'oi_session_submit', 'oi_session_set_stream', 'oi_session_wait', 'oi_session_done',
            'oi_session_destroy', 'oi_nystrom_session_create', 'oi_nystrom_session_submit',
-           'oi_nystrom_session_wait', 'oi_nystrom_session_destroy')
+           'oi_nystrom_session_wait', 'oi_nystrom_session_destroy', 'oi_gpr_predict_multi')
 
 
 class OiOptions(ctypes.Structure):
@@ -67,6 +67,11 @@ def load():
                                      ctypes.c_double, c_double_p, ctypes.c_int32, c_double_p,
                                      c_double_p, c_int32_p, c_int32_p, ctypes.POINTER(OiOptions)]
         lib.oi_gpr_batch.restype = ctypes.c_int
+        lib.oi_gpr_predict_multi.argtypes = [c_double_p, c_double_p, c_int64_p, ctypes.c_int64,
+                                             c_double_p, c_int64_p, ctypes.c_double, c_double_p,
+                                             c_double_p, c_double_p, c_double_p, c_double_p,
+                                             c_int32_p, ctypes.POINTER(OiOptions)]
+        lib.oi_gpr_predict_multi.restype = ctypes.c_int
         lib.oi_nlml_grad_batch.argtypes = [c_double_p, c_double_p, c_double_p, c_int64_p,
                                            ctypes.c_int64, c_double_p, c_double_p, c_double_p,
                                            c_int32_p, ctypes.POINTER(OiOptions)]
@@ -261,6 +266,77 @@ def gpr_batch_device(xyt_dev, z_dev, offs, xs, mean, x0=None, opt=True, hyp=None
                           _ptr(status, ctypes.c_int32), _ptr(inf, ctypes.c_int32), ctypes.byref(o))
     _check(rc)
     return out, status, inf
+
+
+def _multi_targets(offs, xs, toffs, hyp):
+    """Host metadata of oi_gpr_predict_multi, checked: (offs, xs, toffs, hyp, ncell)."""
+    offs = np.ascontiguousarray(offs, dtype=np.int64).reshape(-1)
+    toffs = np.ascontiguousarray(toffs, dtype=np.int64).reshape(-1)
+    xs = np.ascontiguousarray(xs, dtype=np.float64).reshape(-1, 3)
+    ncell = len(offs) - 1
+    if ncell < 0 or len(toffs) != ncell + 1 or offs[0] != 0 or toffs[0] != 0 \
+            or toffs[-1] != xs.shape[0]:
+        raise ValueError("inconsistent ragged batch")
+    hyp = np.ascontiguousarray(hyp, dtype=np.float64).reshape(-1, 5)
+    if hyp.shape[0] != ncell:
+        raise ValueError("hyp must be [ncell x 5]")
+    return offs, xs, toffs, hyp, ncell
+
+
+def _predict_multi(px, pz, offs, xs, toffs, mean, hyp, ncell, cov, lz, o):
+    T = int(toffs[-1])
+    fs = np.empty(T)
+    sd = np.empty(T)
+    lza = np.empty(ncell) if lz else None
+    nt = np.diff(toffs)
+    cova = np.empty(int((nt * nt).sum())) if cov else None
+    status = np.zeros(ncell, dtype=np.int32)
+    rc = load().oi_gpr_predict_multi(px, pz, _ptr(offs, ctypes.c_int64), ncell,
+                                     _ptr(xs, ctypes.c_double), _ptr(toffs, ctypes.c_int64),
+                                     float(mean), _ptr(hyp, ctypes.c_double),
+                                     _ptr(fs, ctypes.c_double), _ptr(sd, ctypes.c_double),
+                                     _ptr(lza, ctypes.c_double), _ptr(cova, ctypes.c_double),
+                                     _ptr(status, ctypes.c_int32), ctypes.byref(o))
+    _check(rc)
+    return fs, sd, lza, cova, status
+
+
+def gpr_predict_multi(xyt, z, offs, xs, toffs, mean, hyp, cov=False, lz=True, **opt_kw):
+    """oi_gpr_predict_multi: predict every cell at its own list of targets
+    (``xs`` [T x 3], cell c owning rows toffs[c]:toffs[c+1]) at LINEAR hypers
+    ``hyp`` [ncell x 5].  Returns (fs [T], sd [T], lz [ncell] | None, cov | None,
+    status [ncell]); ``cov`` is the flat array of the cells' nt x nt posterior
+    covariances back to back (``split_cov`` cuts it up)."""
+    offs, xs, toffs, hyp, ncell = _multi_targets(offs, xs, toffs, hyp)
+    xyt = np.ascontiguousarray(xyt, dtype=np.float64).reshape(-1, 3)
+    z = np.ascontiguousarray(z, dtype=np.float64).reshape(-1)
+    if offs[-1] != len(z) or xyt.shape[0] != len(z):
+        raise ValueError("inconsistent ragged batch")
+    return _predict_multi(_ptr(xyt, ctypes.c_double), _ptr(z, ctypes.c_double), offs, xs, toffs,
+                          mean, hyp, ncell, cov, lz, options(**opt_kw))
+
+
+def gpr_predict_multi_device(xyt_dev, z_dev, offs, xs, toffs, mean, hyp, cov=False, lz=True,
+                             **opt_kw):
+    """gpr_predict_multi with ``xyt_dev`` / ``z_dev`` already resident in HBM
+    (fp64 contiguous torch tensors on cuda:``opt_kw['device']``); targets,
+    offsets and hypers stay on the host.  Runs on torch's current stream."""
+    offs, xs, toffs, hyp, ncell = _multi_targets(offs, xs, toffs, hyp)
+    N = int(offs[-1])
+    dev = int(opt_kw.get('device', 0))
+    _check_dev(xyt_dev, dev, n=3 * N, what='xyt')
+    _check_dev(z_dev, dev, n=N, what='z')
+    opt_kw.setdefault('stream', _caller_stream(dev))
+    return _predict_multi(ctypes.cast(xyt_dev.data_ptr(), c_double_p),
+                          ctypes.cast(z_dev.data_ptr(), c_double_p), offs, xs, toffs, mean, hyp,
+                          ncell, cov, lz, options(device_inputs=True, **opt_kw))
+
+
+def split_cov(cov, toffs):
+    """The flat ``cov`` of gpr_predict_multi as a list of nt x nt arrays (views)."""
+    nt = np.diff(np.asarray(toffs, dtype=np.int64))
+    o = np.concatenate([[0], np.cumsum(nt * nt)])
+    return [cov[o[c]:o[c + 1]].reshape(nt[c], nt[c]) for c in range(len(nt))]
 
 
 class Session:

@@ -126,3 +126,26 @@ def gpr_cells(cells, opt=True, x0=None, hyp=None, info=False, **kw):
     return _lib.gpr_batch(cells.xyt, cells.z, cells.offs, cells.xs, cells.mean,
                           x0=np.asarray(x0, float)[:6] if opt else None, opt=opt,
                           hyp=hyp, info=info, **o)
+
+
+def gpr_cells_multi(cells, xs, toffs, opt=True, x0=None, hyp=None, cov=False, **kw):
+    """Predict every cell of a RaggedCells object at a list of targets of its
+    own -- the notebook's ``GPR(x, y, xs, ...)`` with ``xs`` ns x 3 -- with the
+    full posterior covariance ``Kxs - v'v`` on request.
+
+    ``xs`` [T x 3] holds the targets of all cells, cell c owning rows
+    ``toffs[c]:toffs[c+1]``.  ``opt=True`` fits the hypers exactly as
+    ``gpr_cells(opt=True)`` does (one ``oi_gpr_batch`` call, results unchanged)
+    and predicts at the fitted hypers; ``opt=False`` predicts at ``hyp``
+    [ncell x 5].  Returns ``(fs [T], sd [T], cov_list or None, out8, status)``:
+    ``out8`` is what ``gpr_cells`` returns for the cells' own targets
+    ``cells.xs`` (fs, sd, lZ, hypers), ``cov_list[c]`` the nt_c x nt_c matrix of
+    cell c, ``status[c]`` non-zero where the fit's or the prediction's
+    covariance was not positive definite (NaN outputs)."""
+    o = dict(options)
+    o.update(kw)
+    out8, status, _ = gpr_cells(cells, opt=opt, x0=x0, hyp=hyp, **kw)
+    h = out8[:, 3:8] if opt else np.asarray(hyp, dtype=np.float64).reshape(-1, 5)
+    fs, sd, _, cv, st = _lib.gpr_predict_multi(cells.xyt, cells.z, cells.offs, xs, toffs, cells.mean,
+                                               h, cov=cov, lz=False, **o)
+    return fs, sd, (_lib.split_cov(cv, toffs) if cov else None), out8, np.maximum(status, st)

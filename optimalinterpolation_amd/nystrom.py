@@ -10,6 +10,8 @@ cell 5) fits and predicts with:
   (nlZ (1,), dnlZ (5,)), +inf on LinAlgError.
 * ``GPR(x, y, xs, ell, sf2, sn2, mean, approx=False, M=None, returnprior=False)``
   -- NB1 GPR (fs, sd[, prior sd]); ``M=None`` means ``int(n/5)`` as in NB1.
+  With ``approx=False`` ``xs`` may be NB1's ns x 3 array of targets
+  (``oi_gpr_predict_multi``); ``approx=True`` takes one target per call.
 * ``fit(x, y, M, x0=None)`` / ``fit_batch`` -- ``scipy.optimize.minimize(SMLII, x0,
   args=(x, y, True, M), method='CG', jac=True)`` (NB1 code cell 5) on the
   restated scipy CG of liboi.
@@ -92,13 +94,24 @@ def GPR_batch(xyt, y, offs, xs, hyp, mean, M=None):
 
 
 def GPR(x, y, xs, ell, sf2, sn2, mean, approx=False, M=None, returnprior=False):
-    """NB1 GPR for one cell and one target: (fs, sd[, prior sd])."""
+    """NB1 GPR for one cell: (fs, sd[, prior sd]).  ``xs`` is one target or,
+    with ``approx=False``, NB1's ns x 3 array of targets (fs and sd of length
+    ns, through ``oi_gpr_predict_multi``)."""
     x = np.asarray(x, dtype=np.float64).reshape(-1, 3)
     y = np.asarray(y, dtype=np.float64).reshape(-1)
-    xs = np.asarray(xs, dtype=np.float64).reshape(1, 3)
+    xs = np.asarray(xs, dtype=np.float64).reshape(-1, 3)
+    ns = xs.shape[0]
     offs = np.array([0, len(y)], dtype=np.int64)
     hyp = np.array([[ell[0], ell[1], ell[2], sf2, sn2]], dtype=np.float64)
-    if approx:
+    if ns != 1:
+        if approx:
+            raise NotImplementedError("GPR(approx=True) predicts one target per call; "
+                                      f"got xs with {ns} rows (use approx=False, or call per target)")
+        # the residual outputs with mean 0, the prior mean added back as in NB1
+        f0, sd, _, _, status = _lib.gpr_predict_multi(x, y, offs, xs, [0, ns], 0.0, hyp, lz=False,
+                                                      **options)
+        fs, sp = mean + f0, np.sqrt(sf2)
+    elif approx:
         pred, status = GPR_batch(x, y, offs, xs, hyp, mean, M=None if M is None else [M])
         fs, sd, sp = np.array([[pred[0, 0]]]), np.array([pred[0, 1]]), pred[0, 2]
     else:  # full GP: the main path's predict with the residual outputs and mean 0
