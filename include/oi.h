@@ -225,7 +225,7 @@ int oi_nystrom_fit_batch(const double* xyt, const double* y, const int64_t* offs
  * oi_session_* for the full GP): every submitted batch (oi_nystrom_fit_batch's
  * arguments; host copies of offs, sel, soffs, x0, xs are taken, DEVICE inputs
  * and all outputs must stay valid until the ticket completes) joins one queue;
- * up to OI_NYS_CAP (32) cells per stream group fit at once and finished cells
+ * up to OI_NYS_CAP (64) cells per stream group fit at once and finished cells
  * are replaced from the queue, so a batch's slowest cells overlap later
  * batches.  Per-cell results equal oi_nystrom_fit_batch's bit for bit.
  *   submit returns a ticket >= 0 (or a negative OI_E* code); wait runs rounds

@@ -5,15 +5,18 @@
 // Kernels: oi_day.hip.  Host mode copies through the library; with
 // opts->device_inputs = 1 the array arguments are device pointers (HBM
 // resident) and nothing crosses PCIe except the small host-side arrays named
-// in oi.h (vmax, kern, offs).
+// in oi.h (vmax, kern, offs).  Every device buffer lives for one call and is
+// stream-ordered (DevBuf(bytes, stream)): a radius query issued between a
+// session's rounds (bench.py's timed day) must not drain the rounds in flight
+// on the session's streams, as a synchronous hipFree would.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
-#include <string>
 #include <vector>
 
 #include "../../include/oi.h"
+#include "oi_host.h"
 
 extern "C" {
 int oi_launch_smooth(const double* in, double* out, int nf, int64_t ny, int64_t nx,
@@ -26,70 +29,9 @@ int oi_launch_ball_fill(const double* pts, int64_t M, const double* bbox, const 
 int oi_launch_gather_rows(const double* xt, const double* yt, const double* tt, const double* zt,
                           const int64_t* idx, int64_t N, int64_t M, double* xyt, double* zout,
                           void* stream);
-int oi_set_last_error(int code, const char* msg);  // oi_engine.cpp
 }
 
 namespace {
-
-struct HipErr {
-  std::string msg;
-};
-
-#define HC(expr)                                                                   \
-  do {                                                                             \
-    hipError_t e_ = (expr);                                                        \
-    if (e_ != hipSuccess) throw HipErr{std::string(#expr) + ": " + hipGetErrorString(e_)}; \
-  } while (0)
-
-// device buffer owned for the duration of one call, allocated and freed in
-// the call's stream order: hipFree would synchronise the whole device, so a
-// radius query issued between a session's rounds (bench.py's timed day) would
-// drain the rounds in flight on the session's streams
-struct DBuf {
-  void* p = nullptr;
-  hipStream_t s = nullptr;
-  DBuf() = default;
-  DBuf(size_t bytes, hipStream_t st) : s(st) {
-    if (bytes) HC(hipMallocAsync(&p, bytes, s));
-  }
-  ~DBuf() {
-    if (p) (void)hipFreeAsync(p, s);
-  }
-  DBuf(const DBuf&) = delete;
-  DBuf& operator=(const DBuf&) = delete;
-  template <class T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
-
-struct Ctx {
-  oi_options o;
-  hipStream_t s;
-};
-
-int setup(const oi_options* opts, Ctx& c) {
-  oi_options_default(&c.o);
-  if (opts) c.o = *opts;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return oi_set_last_error(OI_E_NODEV, "no HIP device available");
-  if (c.o.device < 0 || c.o.device >= ndev) return oi_set_last_error(OI_E_ARG, "bad device ordinal");
-  if (hipSetDevice(c.o.device) != hipSuccess) return oi_set_last_error(OI_E_HIP, "hipSetDevice failed");
-  c.s = (hipStream_t)c.o.stream;
-  return 0;
-}
-
-template <class F>
-int guarded(F&& f) {
-  try {
-    return f();
-  } catch (const HipErr& e) {
-    return oi_set_last_error(OI_E_HIP, e.msg.c_str());
-  } catch (const std::bad_alloc&) {
-    return oi_set_last_error(OI_E_NOMEM, "allocation failed");
-  }
-}
 
 // astropy Gaussian2DKernel(x_stddev=std): Gaussian2D(amplitude 1/(2 pi std^2),
 // theta 0) sampled at integer offsets, size 8*std rounded up to odd, / sum.
@@ -128,27 +70,28 @@ int oi_smooth_fields(const double* fields, int32_t nf, int64_t ny, int64_t nx, c
     if (!(std_ > 0.0) || std_ > 8.0) return oi_set_last_error(OI_E_ARG, "std must be in (0, 8]");
     kv = gaussian_kernel(std_, ks);
   }
-  Ctx c;
-  if (int rc = setup(opts, c)) return rc;
-  return guarded([&] {
+  const oi_options o = oi_resolve(opts);
+  if (int rc = oi_select_device(o)) return rc;
+  hipStream_t st = (hipStream_t)o.stream;
+  return oi_guarded([&] {
     const size_t npix = (size_t)ny * nx, fb = (size_t)nf * npix * 8;
-    DBuf dk(kv.size() * 8, c.s), dv((size_t)nf * 8, c.s);
-    HC(hipMemcpyAsync(dk.p, kv.data(), kv.size() * 8, hipMemcpyHostToDevice, c.s));
-    HC(hipMemcpyAsync(dv.p, vmax, (size_t)nf * 8, hipMemcpyHostToDevice, c.s));
-    if (c.o.device_inputs) {
-      if (oi_launch_smooth(fields, out, nf, ny, nx, dv.as<double>(), dk.as<double>(), ks, mask, c.s))
+    DevBuf dk(kv.size() * 8, st), dv((size_t)nf * 8, st);
+    HC(hipMemcpyAsync(dk.p, kv.data(), kv.size() * 8, hipMemcpyHostToDevice, st));
+    HC(hipMemcpyAsync(dv.p, vmax, (size_t)nf * 8, hipMemcpyHostToDevice, st));
+    if (o.device_inputs) {
+      if (oi_launch_smooth(fields, out, nf, ny, nx, dv.as<double>(), dk.as<double>(), ks, mask, st))
         throw HipErr{"smooth kernel launch failed"};
-      HC(hipStreamSynchronize(c.s));
+      HC(hipStreamSynchronize(st));
       return 0;
     }
-    DBuf din(fb, c.s), dout(fb, c.s), dm(npix * 8, c.s);
-    HC(hipMemcpyAsync(din.p, fields, fb, hipMemcpyHostToDevice, c.s));
-    HC(hipMemcpyAsync(dm.p, mask, npix * 8, hipMemcpyHostToDevice, c.s));
+    DevBuf din(fb, st), dout(fb, st), dm(npix * 8, st);
+    HC(hipMemcpyAsync(din.p, fields, fb, hipMemcpyHostToDevice, st));
+    HC(hipMemcpyAsync(dm.p, mask, npix * 8, hipMemcpyHostToDevice, st));
     if (oi_launch_smooth(din.as<double>(), dout.as<double>(), nf, ny, nx, dv.as<double>(),
-                         dk.as<double>(), ks, dm.as<double>(), c.s))
+                         dk.as<double>(), ks, dm.as<double>(), st))
       throw HipErr{"smooth kernel launch failed"};
-    HC(hipMemcpyAsync(out, dout.p, fb, hipMemcpyDeviceToHost, c.s));
-    HC(hipStreamSynchronize(c.s));
+    HC(hipMemcpyAsync(out, dout.p, fb, hipMemcpyDeviceToHost, st));
+    HC(hipStreamSynchronize(st));
     return 0;
   });
 }
@@ -161,35 +104,36 @@ int oi_ball_query(const double* pts, int64_t M, const double* q, int64_t Q, doub
   if (Q == 0) return 0;
   if (!q || (M > 0 && !pts)) return oi_set_last_error(OI_E_ARG, "null pointer");
   if (!(r >= 0.0)) return oi_set_last_error(OI_E_ARG, "radius must be >= 0");
-  Ctx c;
-  if (int rc = setup(opts, c)) return rc;
-  return guarded([&] {
+  const oi_options o = oi_resolve(opts);
+  if (int rc = oi_select_device(o)) return rc;
+  hipStream_t st = (hipStream_t)o.stream;
+  return oi_guarded([&] {
     const double r2 = r * r;
-    const bool dev = c.o.device_inputs != 0;
-    DBuf dpts(dev ? 0 : (size_t)M * 16, c.s), dq(dev ? 0 : (size_t)Q * 16, c.s);
+    const bool dev = o.device_inputs != 0;
+    DevBuf dpts(dev ? 0 : (size_t)M * 16, st), dq(dev ? 0 : (size_t)Q * 16, st);
     const double* P = dev ? pts : dpts.as<double>();
     const double* Qp = dev ? q : dq.as<double>();
     if (!dev) {
-      if (M) HC(hipMemcpyAsync(dpts.p, pts, (size_t)M * 16, hipMemcpyHostToDevice, c.s));
-      HC(hipMemcpyAsync(dq.p, q, (size_t)Q * 16, hipMemcpyHostToDevice, c.s));
+      if (M) HC(hipMemcpyAsync(dpts.p, pts, (size_t)M * 16, hipMemcpyHostToDevice, st));
+      HC(hipMemcpyAsync(dq.p, q, (size_t)Q * 16, hipMemcpyHostToDevice, st));
     }
-    DBuf bbox((size_t)((M + 255) / 256 + 1) * 32, c.s), cnt((size_t)Q * 8, c.s);
-    if (oi_launch_ball_count(P, M, bbox.as<double>(), Qp, Q, r2, cnt.as<int64_t>(), c.s))
+    DevBuf bbox((size_t)((M + 255) / 256 + 1) * 32, st), cnt((size_t)Q * 8, st);
+    if (oi_launch_ball_count(P, M, bbox.as<double>(), Qp, Q, r2, cnt.as<int64_t>(), st))
       throw HipErr{"ball count launch failed"};
     std::vector<int64_t> h((size_t)Q);
-    HC(hipMemcpyAsync(h.data(), cnt.p, (size_t)Q * 8, hipMemcpyDeviceToHost, c.s));
-    HC(hipStreamSynchronize(c.s));
+    HC(hipMemcpyAsync(h.data(), cnt.p, (size_t)Q * 8, hipMemcpyDeviceToHost, st));
+    HC(hipStreamSynchronize(st));
     for (int64_t k = 0; k < Q; ++k) offs[k + 1] = offs[k] + h[(size_t)k];
     const int64_t total = offs[Q];
     if (!idx || total > cap || total == 0) return 0;  // caller sizes idx from offs[Q]
-    DBuf doffs((size_t)(Q + 1) * 8, c.s);
-    HC(hipMemcpyAsync(doffs.p, offs, (size_t)(Q + 1) * 8, hipMemcpyHostToDevice, c.s));
-    DBuf didx(dev ? 0 : (size_t)total * 8, c.s);
+    DevBuf doffs((size_t)(Q + 1) * 8, st);
+    HC(hipMemcpyAsync(doffs.p, offs, (size_t)(Q + 1) * 8, hipMemcpyHostToDevice, st));
+    DevBuf didx(dev ? 0 : (size_t)total * 8, st);
     int64_t* I = dev ? idx : didx.as<int64_t>();
-    if (oi_launch_ball_fill(P, M, bbox.as<double>(), Qp, Q, r2, doffs.as<int64_t>(), I, c.s))
+    if (oi_launch_ball_fill(P, M, bbox.as<double>(), Qp, Q, r2, doffs.as<int64_t>(), I, st))
       throw HipErr{"ball fill launch failed"};
-    if (!dev) HC(hipMemcpyAsync(idx, didx.p, (size_t)total * 8, hipMemcpyDeviceToHost, c.s));
-    HC(hipStreamSynchronize(c.s));
+    if (!dev) HC(hipMemcpyAsync(idx, didx.p, (size_t)total * 8, hipMemcpyDeviceToHost, st));
+    HC(hipStreamSynchronize(st));
     return 0;
   });
 }
@@ -201,30 +145,31 @@ int oi_gather_rows(const double* x_train, const double* y_train, const double* t
   if (N == 0) return 0;
   if (!x_train || !y_train || !t_train || !z || !idx || !xyt || !zout)
     return oi_set_last_error(OI_E_ARG, "null pointer");
-  Ctx c;
-  if (int rc = setup(opts, c)) return rc;
-  return guarded([&] {
-    if (c.o.device_inputs) {
-      if (oi_launch_gather_rows(x_train, y_train, t_train, z, idx, N, M, xyt, zout, c.s))
+  const oi_options o = oi_resolve(opts);
+  if (int rc = oi_select_device(o)) return rc;
+  hipStream_t st = (hipStream_t)o.stream;
+  return oi_guarded([&] {
+    if (o.device_inputs) {
+      if (oi_launch_gather_rows(x_train, y_train, t_train, z, idx, N, M, xyt, zout, st))
         throw HipErr{"gather launch failed"};
-      HC(hipStreamSynchronize(c.s));
+      HC(hipStreamSynchronize(st));
       return 0;
     }
     for (int64_t k = 0; k < N; ++k)
       if (idx[k] < 0 || idx[k] >= M) return oi_set_last_error(OI_E_ARG, "index out of range");
-    DBuf dx((size_t)M * 8, c.s), dy((size_t)M * 8, c.s), dt((size_t)M * 8, c.s), dz((size_t)M * 8, c.s),
-        di((size_t)N * 8, c.s), dxyt((size_t)N * 24, c.s), dzo((size_t)N * 8, c.s);
-    HC(hipMemcpyAsync(dx.p, x_train, (size_t)M * 8, hipMemcpyHostToDevice, c.s));
-    HC(hipMemcpyAsync(dy.p, y_train, (size_t)M * 8, hipMemcpyHostToDevice, c.s));
-    HC(hipMemcpyAsync(dt.p, t_train, (size_t)M * 8, hipMemcpyHostToDevice, c.s));
-    HC(hipMemcpyAsync(dz.p, z, (size_t)M * 8, hipMemcpyHostToDevice, c.s));
-    HC(hipMemcpyAsync(di.p, idx, (size_t)N * 8, hipMemcpyHostToDevice, c.s));
+    DevBuf dx((size_t)M * 8, st), dy((size_t)M * 8, st), dt((size_t)M * 8, st), dz((size_t)M * 8, st),
+        di((size_t)N * 8, st), dxyt((size_t)N * 24, st), dzo((size_t)N * 8, st);
+    HC(hipMemcpyAsync(dx.p, x_train, (size_t)M * 8, hipMemcpyHostToDevice, st));
+    HC(hipMemcpyAsync(dy.p, y_train, (size_t)M * 8, hipMemcpyHostToDevice, st));
+    HC(hipMemcpyAsync(dt.p, t_train, (size_t)M * 8, hipMemcpyHostToDevice, st));
+    HC(hipMemcpyAsync(dz.p, z, (size_t)M * 8, hipMemcpyHostToDevice, st));
+    HC(hipMemcpyAsync(di.p, idx, (size_t)N * 8, hipMemcpyHostToDevice, st));
     if (oi_launch_gather_rows(dx.as<double>(), dy.as<double>(), dt.as<double>(), dz.as<double>(),
-                              di.as<int64_t>(), N, M, dxyt.as<double>(), dzo.as<double>(), c.s))
+                              di.as<int64_t>(), N, M, dxyt.as<double>(), dzo.as<double>(), st))
       throw HipErr{"gather launch failed"};
-    HC(hipMemcpyAsync(xyt, dxyt.p, (size_t)N * 24, hipMemcpyDeviceToHost, c.s));
-    HC(hipMemcpyAsync(zout, dzo.p, (size_t)N * 8, hipMemcpyDeviceToHost, c.s));
-    HC(hipStreamSynchronize(c.s));
+    HC(hipMemcpyAsync(xyt, dxyt.p, (size_t)N * 24, hipMemcpyDeviceToHost, st));
+    HC(hipMemcpyAsync(zout, dzo.p, (size_t)N * 8, hipMemcpyDeviceToHost, st));
+    HC(hipStreamSynchronize(st));
     return 0;
   });
 }

@@ -29,6 +29,7 @@
 #include "../../include/oi.h"
 #include "cg.hpp"
 #include "oi_device.h"
+#include "oi_host.h"
 #include "oi_masks.h"
 
 namespace {
@@ -40,18 +41,6 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
-#define HIPC(expr)                                                                            \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess)                                                                     \
-      throw HipError(std::string(#expr) + ": " + hipGetErrorString(e_));                      \
-  } while (0)
-
-struct HipError {
-  std::string msg;
-  explicit HipError(std::string m) : msg(std::move(m)) {}
-};
-
 inline int tiles_of(int64_t n) { return (int)((n + OI_NB - 1) / OI_NB); }
 
 // ------------------------------------------------------------- arena
@@ -59,7 +48,7 @@ inline int tiles_of(int64_t n) { return (int)((n + OI_NB - 1) / OI_NB); }
 class Arena {
  public:
   void init(size_t bytes) {
-    HIPC(hipMalloc(&base_, bytes));
+    HC(hipMalloc(&base_, bytes));
     size_ = bytes;
     free_.clear();
     free_[0] = bytes;
@@ -389,7 +378,7 @@ struct Context {
   hipStream_t aux_stream(int g) {
     while ((int)aux.size() < g) {
       hipStream_t s;
-      HIPC(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+      HC(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
       aux.push_back(s);
     }
     return aux[g - 1];
@@ -409,16 +398,16 @@ Context& context(int device, int64_t pool_bytes) {
   if (!p) {
     p = std::make_unique<Context>();
     p->device = device;
-    HIPC(hipSetDevice(device));
-    HIPC(hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking));
-    HIPC(hipStreamCreateWithFlags(&p->sub_stream, hipStreamNonBlocking));
+    HC(hipSetDevice(device));
+    HC(hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking));
+    HC(hipStreamCreateWithFlags(&p->sub_stream, hipStreamNonBlocking));
   }
-  HIPC(hipSetDevice(device));
+  HC(hipSetDevice(device));
   size_t want = (size_t)pool_bytes;
   if (want == 0) {
     if (p->arena_bytes == SIZE_MAX - 1) return *p;  // keep the automatic arena between calls
     size_t fr = 0, tot = 0;
-    HIPC(hipMemGetInfo(&fr, &tot));
+    HC(hipMemGetInfo(&fr, &tot));
     // OI_ARENA_FRAC: the share of free HBM the automatic arena takes (0.6);
     // bench.py lowers it when several rank processes share one GPU
     static const double frac = [] {
@@ -439,7 +428,7 @@ Context& context(int device, int64_t pool_bytes) {
       try {
         p->arena.init(want);
         break;
-      } catch (const HipError&) {
+      } catch (const HipErr&) {
         (void)hipGetLastError();
         if (!automatic || want < (size_t(1) << 30)) throw;
         want /= 2;
@@ -456,9 +445,9 @@ struct DBuf {
   size_t n = 0;
   void reserve(size_t bytes) {
     if (bytes <= n) return;
-    if (p) HIPC(hipFree(p));
+    if (p) HC(hipFree(p));
     p = nullptr;
-    HIPC(hipMalloc(&p, bytes));
+    HC(hipMalloc(&p, bytes));
     n = bytes;
   }
   ~DBuf() {
@@ -470,9 +459,9 @@ struct HBuf {  // pinned host
   size_t n = 0;
   void reserve(size_t bytes, unsigned flags = hipHostMallocDefault) {
     if (bytes <= n) return;
-    if (p) HIPC(hipHostFree(p));
+    if (p) HC(hipHostFree(p));
     p = nullptr;
-    HIPC(hipHostMalloc(&p, bytes, flags));
+    HC(hipHostMalloc(&p, bytes, flags));
     n = bytes;
   }
   ~HBuf() {
@@ -547,7 +536,7 @@ class Engine {
       : ctx_(ctx), o_(o), legacy_(legacy_panels()), panel4_(panel4_enabled()),
         panel4_minj_(panel4_minj()), panel4_mint_(panel4_mint()), panel4_minwg_(panel4_minwg()),
         fuse_diag_min_(fuse_diag_min()) {
-    HIPC(hipSetDevice(ctx.device));
+    HC(hipSetDevice(ctx.device));
     st_ = o.stream ? (hipStream_t)o.stream : ctx.own_stream;
     ss_ = ctx.sub_stream;
     static const bool debug_set = [] {
@@ -577,12 +566,12 @@ class Engine {
     // memory the kernels write directly (k_finalize), no D2H copy per round
     h_res_.reserve(cap_ * OI_OUT_N * 8, hipHostMallocCoherent | hipHostMallocMapped);
     hres_ = (double*)h_res_.p;
-    HIPC(hipHostGetDevicePointer((void**)&dres_, hres_, 0));
+    HC(hipHostGetDevicePointer((void**)&dres_, hres_, 0));
     h_flag_.reserve(G_ * 64, hipHostMallocCoherent | hipHostMallocMapped);
     std::memset(h_flag_.p, 0, G_ * 64);
-    HIPC(hipHostGetDevicePointer((void**)&dflag_, h_flag_.p, 0));
+    HC(hipHostGetDevicePointer((void**)&dflag_, h_flag_.p, 0));
     d_done_.reserve(G_ * 64);
-    HIPC(hipMemset(d_done_.p, 0, G_ * 64));
+    HC(hipMemset(d_done_.p, 0, G_ * 64));
     groups_.resize(G_);
     for (int g = 0; g < G_; ++g) {
       Group& gr = groups_[g];
@@ -600,10 +589,10 @@ class Engine {
       gr.dstat = gr.dl + 3 * capG_;
       if (o.profile) {
         gr.ev.resize(2 * (3 * 1024 + 16));
-        for (auto& ee : gr.ev) HIPC(hipEventCreate(&ee));
+        for (auto& ee : gr.ev) HC(hipEventCreate(&ee));
       }
     }
-    HIPC(hipEventCreateWithFlags(&ready_, hipEventDisableTiming));
+    HC(hipEventCreateWithFlags(&ready_, hipEventDisableTiming));
     t_start_ = std::chrono::steady_clock::now();
   }
 
@@ -630,9 +619,9 @@ class Engine {
     // device inputs: order after the caller's stream (or the legacy null
     // stream, torch's default) so producers of xyt / y / mX have finished
     if (o_.device_inputs && N > 0) {
-      HIPC(hipEventRecord(ready_, o_.stream ? (hipStream_t)o_.stream : (hipStream_t)0));
-      for (Group& gr : groups_) HIPC(hipStreamWaitEvent(gr.st, ready_, 0));
-      HIPC(hipStreamWaitEvent(ss_, ready_, 0));
+      HC(hipEventRecord(ready_, o_.stream ? (hipStream_t)o_.stream : (hipStream_t)0));
+      for (Group& gr : groups_) HC(hipStreamWaitEvent(gr.st, ready_, 0));
+      HC(hipStreamWaitEvent(ss_, ready_, 0));
     }
     // The submission's own work (residuals, copies, k_dedup, the m / SSW
     // read-back) runs on the submit stream: the host waits for it alone, not
@@ -670,15 +659,15 @@ class Engine {
     const double* d_x = xyt_in;
     if (o_.device_inputs) {
       if (N > 0 && oi_launch_residual(y, mX, jb.mean, d_r, N, ss_))
-        throw HipError("residual kernel launch failed");
+        throw HipErr{"residual kernel launch failed"};
     } else {
       double* dx = (double*)take(sz[7]);
       d_x = dx;
       if (N > 0) {
         jb.r_host.resize(N);
         for (int64_t a = 0; a < N; ++a) jb.r_host[a] = y[a] - (mX ? mX[a] : 1.0 * jb.mean);
-        HIPC(hipMemcpyAsync(dx, xyt_in, N * 3 * 8, hipMemcpyHostToDevice, ss_));
-        HIPC(hipMemcpyAsync(d_r, jb.r_host.data(), N * 8, hipMemcpyHostToDevice, ss_));
+        HC(hipMemcpyAsync(dx, xyt_in, N * 3 * 8, hipMemcpyHostToDevice, ss_));
+        HC(hipMemcpyAsync(d_r, jb.r_host.data(), N * 8, hipMemcpyHostToDevice, ss_));
       }
     }
     // distinct sites of every cell; the host needs m to size and order cells
@@ -687,14 +676,14 @@ class Engine {
     if (nc > 0) {
       int64_t maxn = 0;
       for (int64_t c = 0; c < nc; ++c) maxn = std::max(maxn, jb.offs[c + 1] - jb.offs[c]);
-      HIPC(hipMemcpyAsync(d_offs, jb.offs.data(), (nc + 1) * 8, hipMemcpyHostToDevice, ss_));
+      HC(hipMemcpyAsync(d_offs, jb.offs.data(), (nc + 1) * 8, hipMemcpyHostToDevice, ss_));
       if (oi_launch_dedup(d_x, d_r, d_offs, (int)nc, (int)std::min<int64_t>(maxn, INT32_MAX),
                           dedup_enabled() ? 0 : 1, d_sites, d_v, d_dw, d_m, d_ssw, ss_))
-        throw HipError(std::string("dedup kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-      HIPC(hipMemcpyAsync(jb.m.data(), d_m, nc * 4, hipMemcpyDeviceToHost, ss_));
-      HIPC(hipMemcpyAsync(jb.ssw.data(), d_ssw, nc * 8, hipMemcpyDeviceToHost, ss_));
+        throw HipErr{std::string("dedup kernel launch failed: ") + hipGetErrorString(hipGetLastError())};
+      HC(hipMemcpyAsync(jb.m.data(), d_m, nc * 4, hipMemcpyDeviceToHost, ss_));
+      HC(hipMemcpyAsync(jb.ssw.data(), d_ssw, nc * 8, hipMemcpyDeviceToHost, ss_));
     }
-    HIPC(hipStreamSynchronize(ss_));  // m known; host inputs may be released on return
+    HC(hipStreamSynchronize(ss_));  // m known; host inputs may be released on return
     jb.xyt = d_x;
     jb.r = d_r;
     jb.sites = d_sites;
@@ -708,8 +697,8 @@ class Engine {
       // of the arena to return
       if (jb.in_off != SIZE_MAX) ctx_.arena.release(jb.in_off, jb.in_bytes);
       jb.in_off = SIZE_MAX;
-      throw NoMem("a cell needs " + std::to_string(max_cell) + " bytes of workspace, pool is " +
-                  std::to_string(ctx_.arena.size()));
+      throw NoMem{"a cell needs " + std::to_string(max_cell) + " bytes of workspace, pool is " +
+                  std::to_string(ctx_.arena.size())};
     }
     // (the submission completed on the host's clock: every group stream's later
     // launches see its outputs)
@@ -759,7 +748,7 @@ class Engine {
       }
       if (id >= 0 ? done(id) : (jobs_.empty() && !any)) break;
       if (!any) {
-        if (!queue_.empty()) throw NoMem("workspace exhausted with no resident cell");
+        if (!queue_.empty()) throw NoMem{"workspace exhausted with no resident cell"};
         break;
       }
     }
@@ -769,11 +758,6 @@ class Engine {
     wall_s_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw).count();
     flush_stats();
   }
-
-  struct NoMem {
-    std::string msg;
-    explicit NoMem(std::string m) : msg(std::move(m)) {}
-  };
 
  private:
   struct Group {
@@ -827,7 +811,7 @@ class Engine {
       sl.off = off;
       sl.bytes = bytes;
       if (poison_)  // debug: NaN-fill the cell's workspace so any read-before-write shows
-        HIPC(hipMemsetAsync(ctx_.arena.ptr(off), 0xFF, bytes, gr.st));
+        HC(hipMemsetAsync(ctx_.arena.ptr(off), 0xFF, bytes, gr.st));
       OiCell& cd = hcell(s);
       std::memset(&cd, 0, sizeof(cd));
       const int T = tiles_of(n);
@@ -917,7 +901,7 @@ class Engine {
     gr.maxT = maxT;
 
     std::memset(gr.hstat, 0, (size_t)capG_ * 4);
-    HIPC(hipMemcpyAsync(gr.dc, gr.hc, blk_, hipMemcpyHostToDevice, gst));
+    HC(hipMemcpyAsync(gr.dc, gr.hc, blk_, hipMemcpyHostToDevice, gst));
     const int32_t* dl_all = gr.dl;
     const int32_t* dl_ev = gr.dl + capG_;
     const OiCell* dc = gr.dc;
@@ -932,7 +916,7 @@ class Engine {
         gr.ev_meta.emplace_back(cur_j, cur_cells);
       }
       const size_t idx = 2 * (gr.ev_kind.size() - 1) + (end ? 1 : 0);
-      if (idx < gr.ev.size()) HIPC(hipEventRecord(gr.ev[idx], gst));
+      if (idx < gr.ev.size()) HC(hipEventRecord(gr.ev[idx], gst));
     };
     int rc = 0;
     cur_cells = na;
@@ -1007,7 +991,7 @@ class Engine {
     rc |= oi_launch_finalize(dc, dl_all, na, (unsigned*)d_done_.p + 16 * g,
                              gr.flagged ? (unsigned long long*)(dflag_ + 64 * g) : nullptr, ++gr.seq, gst);
     mark(K_FINAL, true);
-    if (rc) throw HipError(std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+    if (rc) throw HipErr{std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError())};
     if (o_.profile) {
       for (int k = 0; k < ne; ++k) {
         const OiCell& cd = hc(gr.ev_slots[k]);
@@ -1023,7 +1007,7 @@ class Engine {
   // every ~1 ms so a failed launch surfaces as an error instead of a hang.
   void wait_round(Group& gr) {
     if (!gr.flagged) {
-      HIPC(hipStreamSynchronize(gr.st));
+      HC(hipStreamSynchronize(gr.st));
       return;
     }
     const int g = (int)(&gr - groups_.data());
@@ -1036,8 +1020,8 @@ class Engine {
       last = now;
       const hipError_t e = hipStreamQuery(gr.st);
       if (e == hipErrorNotReady) continue;
-      if (e != hipSuccess) throw HipError(std::string("round failed: ") + hipGetErrorString(e));
-      if (*f != gr.seq) throw HipError("round completed without its completion flag");
+      if (e != hipSuccess) throw HipErr{std::string("round failed: ") + hipGetErrorString(e)};
+      if (*f != gr.seq) throw HipErr{"round completed without its completion flag"};
     }
     std::atomic_thread_fence(std::memory_order_acquire);
   }
@@ -1052,7 +1036,7 @@ class Engine {
       std::vector<LaunchRec> recs;
       for (size_t q = 0; q < gr.ev_kind.size() && 2 * q + 1 < gr.ev.size(); ++q) {
         float a = 0;
-        HIPC(hipEventElapsedTime(&a, gr.ev[2 * q], gr.ev[2 * q + 1]));
+        HC(hipEventElapsedTime(&a, gr.ev[2 * q], gr.ev[2 * q + 1]));
         kms_[gr.ev_kind[q]] += a;
         kln_[gr.ev_kind[q]]++;
         recs.push_back({gr.ev_kind[q], gr.ev_meta[q].first, gr.ev_meta[q].second, (double)a});
@@ -1190,20 +1174,6 @@ bool check_offs(const int64_t* offs, int64_t ncell) {
   return true;
 }
 
-oi_options resolve(const oi_options* opts) {
-  oi_options o;
-  oi_options_default(&o);
-  if (opts) o = *opts;
-  return o;
-}
-
-int check_device(const oi_options& o) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(OI_E_NODEV, "no HIP device available");
-  if (o.device < 0 || o.device >= ndev) return fail(OI_E_ARG, "bad device ordinal");
-  return 0;
-}
-
 // Validates the oi_gpr_batch arguments and fills a Job (host metadata copied).
 int make_gpr_job(const double* xyt, const double* z, const int64_t* offs, int64_t ncell,
                  const double* xs, double mean, const double* x0, int32_t opt, const double* hyp,
@@ -1234,8 +1204,8 @@ int make_gpr_job(const double* xyt, const double* z, const int64_t* offs, int64_
 // One-shot batch: a private engine, submit + drain.
 int run_once(std::unique_ptr<Job> job, const double* xyt, const double* y, const double* mX,
              const oi_options& o) {
-  try {
-    if (int rc = check_device(o)) return rc;
+  if (int rc = oi_select_device(o)) return rc;
+  return oi_guarded([&] {
     if (job->ncell == 0) return 0;
     Context& ctx = context(o.device, o.pool_bytes);
     std::lock_guard<std::mutex> lk(ctx.mu);
@@ -1249,13 +1219,7 @@ int run_once(std::unique_ptr<Job> job, const double* xyt, const double* y, const
     }
     eng.wait(-1);
     return 0;
-  } catch (const HipError& e) {
-    return fail(OI_E_HIP, e.msg);
-  } catch (const Engine::NoMem& e) {
-    return fail(OI_E_NOMEM, e.msg);
-  } catch (const std::bad_alloc&) {
-    return fail(OI_E_NOMEM, "host allocation failed");
-  }
+  });
 }
 
 }  // namespace
@@ -1281,7 +1245,7 @@ int oi_gpr_batch(const double* xyt, const double* z, const int64_t* offs, int64_
                  double* out, int32_t* status, int32_t* info, const oi_options* opts) {
   if (ncell < 0 || !check_offs(offs, ncell)) return fail(OI_E_ARG, "bad offs / ncell");
   if (ncell == 0) return 0;
-  const oi_options o = resolve(opts);
+  const oi_options o = oi_resolve(opts);
   std::unique_ptr<Job> job;
   if (int rc = make_gpr_job(xyt, z, offs, ncell, xs, mean, x0, opt, hyp, out, status, info, o, job))
     return rc;
@@ -1304,7 +1268,7 @@ int oi_nlml_grad_batch(const double* xyt, const double* y, const double* mX, con
   job->nlz = nlz;
   job->grad = grad;
   job->status = status;
-  return run_once(std::move(job), xyt, y, mX, resolve(opts));
+  return run_once(std::move(job), xyt, y, mX, oi_resolve(opts));
 }
 
 // ---- session: continuous batching across calls
@@ -1315,22 +1279,19 @@ struct oi_session {
 };
 
 oi_session* oi_session_create(const oi_options* opts) {
-  const oi_options o = resolve(opts);
-  try {
-    if (check_device(o)) return nullptr;
-    auto* s = new oi_session();
+  const oi_options o = oi_resolve(opts);
+  if (oi_select_device(o)) return nullptr;
+  std::unique_ptr<oi_session> s;
+  const int rc = oi_guarded([&] {
+    s = std::make_unique<oi_session>();
     s->o = o;
     s->ctx = &context(o.device, o.pool_bytes);
     std::lock_guard<std::mutex> lk(s->ctx->mu);
     s->eng = std::make_unique<Engine>(*s->ctx, o, INT64_MAX);
     s->ctx->live_sessions++;
-    return s;
-  } catch (const HipError& e) {
-    fail(OI_E_HIP, e.msg);
-  } catch (const std::bad_alloc&) {
-    fail(OI_E_NOMEM, "host allocation failed");
-  }
-  return nullptr;
+    return 0;
+  });
+  return rc ? nullptr : s.release();
 }
 
 int64_t oi_session_submit(oi_session* s, const double* xyt, const double* z, const int64_t* offs,
@@ -1340,17 +1301,11 @@ int64_t oi_session_submit(oi_session* s, const double* xyt, const double* z, con
   std::unique_ptr<Job> job;
   if (int rc = make_gpr_job(xyt, z, offs, ncell, xs, mean, x0, opt, hyp, out, status, info, s->o, job))
     return rc;
-  try {
+  return oi_guarded([&] {
     std::lock_guard<std::mutex> lk(s->ctx->mu);
-    HIPC(hipSetDevice(s->o.device));
+    HC(hipSetDevice(s->o.device));
     return s->eng->submit(std::move(job), xyt, z, nullptr);
-  } catch (const HipError& e) {
-    return fail(OI_E_HIP, e.msg);
-  } catch (const Engine::NoMem& e) {
-    return fail(OI_E_NOMEM, e.msg);
-  } catch (const std::bad_alloc&) {
-    return fail(OI_E_NOMEM, "host allocation failed");
-  }
+  });
 }
 
 int oi_session_set_stream(oi_session* s, void* stream) {
@@ -1362,18 +1317,12 @@ int oi_session_set_stream(oi_session* s, void* stream) {
 
 int oi_session_wait(oi_session* s, int64_t ticket) {
   if (!s) return fail(OI_E_ARG, "null session");
-  try {
+  return oi_guarded([&] {
     std::lock_guard<std::mutex> lk(s->ctx->mu);
-    HIPC(hipSetDevice(s->o.device));
+    HC(hipSetDevice(s->o.device));
     s->eng->wait(ticket < 0 ? -1 : ticket);
     return 0;
-  } catch (const HipError& e) {
-    return fail(OI_E_HIP, e.msg);
-  } catch (const Engine::NoMem& e) {
-    return fail(OI_E_NOMEM, e.msg);
-  } catch (const std::bad_alloc&) {
-    return fail(OI_E_NOMEM, "host allocation failed");
-  }
+  });
 }
 
 int oi_session_done(oi_session* s, int64_t ticket) {

@@ -15,11 +15,12 @@
 #include <string>
 #include <vector>
 
+#include "oi_host.h"
+
 namespace oila {
 
-struct LinalgErr {  // thrown by the host routines on a HIP error or an operand too large
-  std::string msg;
-};
+// thrown by the host routines on a HIP error or an operand too large
+using LinalgErr = ::HipErr;
 
 // C = alpha op(A) op(B) + beta C  (m x n, inner dimension k); tri:
 //   0  all output tiles;

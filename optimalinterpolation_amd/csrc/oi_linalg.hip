@@ -55,12 +55,6 @@
 
 namespace oila {
 
-#define LC(expr)                                                                                \
-  do {                                                                                          \
-    hipError_t e_ = (expr);                                                                     \
-    if (e_ != hipSuccess) throw LinalgErr{std::string(#expr) + ": " + hipGetErrorString(e_)}; \
-  } while (0)
-
 // Global-address-space views of the descriptors' pointers: plain accesses
 // through generic pointers compile to flat_* instructions, which count
 // against lgkmcnt too, so every LDS wait would also wait for the loads in
@@ -1438,15 +1432,15 @@ const void* Stager::put_bytes(const void* p, size_t bytes) {
   if (need > cap_) {
     if (host_) retired_.push_back({host_, dev_});  // still referenced by queued copies / launches
     size_t nc = std::max<size_t>(1 << 20, 2 * need);
-    LC(hipHostMalloc((void**)&host_, nc, hipHostMallocDefault));
-    LC(hipMalloc((void**)&dev_, nc));
+    HC(hipHostMalloc((void**)&host_, nc, hipHostMallocDefault));
+    HC(hipMalloc((void**)&dev_, nc));
     cap_ = nc;
     off_ = 0;
   }
   char* h = host_ + off_;
   char* d = dev_ + off_;
   std::memcpy(h, p, bytes);
-  LC(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st_));
+  HC(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st_));
   off_ = (off_ + bytes + 255) & ~(size_t)255;
   return d;
 }
@@ -1492,7 +1486,7 @@ void gemm(Stager& S, hipStream_t st, bool ta, bool tb, const std::vector<Gemm>& 
     else if (ta) hipLaunchKernelGGL((k_gemm128<true, false>), grid2, dim3(512), 0, st, dg);
     else if (tb) hipLaunchKernelGGL((k_gemm128<false, true>), grid2, dim3(512), 0, st, dg);
     else hipLaunchKernelGGL((k_gemm128<false, false>), grid2, dim3(512), 0, st, dg);
-    LC(hipGetLastError());
+    HC(hipGetLastError());
     return;
   }
   dim3 grid((unsigned)tiles, (unsigned)live.size());
@@ -1500,7 +1494,7 @@ void gemm(Stager& S, hipStream_t st, bool ta, bool tb, const std::vector<Gemm>& 
   else if (ta) hipLaunchKernelGGL((k_gemm<true, false>), grid, dim3(256), 0, st, dg);
   else if (tb) hipLaunchKernelGGL((k_gemm<false, true>), grid, dim3(256), 0, st, dg);
   else hipLaunchKernelGGL((k_gemm<false, false>), grid, dim3(256), 0, st, dg);
-  LC(hipGetLastError());
+  HC(hipGetLastError());
 }
 
 void gemv(Stager& S, hipStream_t st, bool trans, const std::vector<Gemv>& g) {
@@ -1519,7 +1513,7 @@ void gemv(Stager& S, hipStream_t st, bool trans, const std::vector<Gemv>& g) {
   else
     hipLaunchKernelGGL(k_gemv_n, dim3((unsigned)((outs + 63) / 64), (unsigned)live.size()), dim3(64 * GV_W), 0,
                        st, dg);
-  LC(hipGetLastError());
+  HC(hipGetLastError());
 }
 
 void cholesky(Stager& S, hipStream_t st, const std::vector<Chol>& cs) {
@@ -1532,7 +1526,7 @@ void cholesky(Stager& S, hipStream_t st, const std::vector<Chol>& cs) {
   const Chol* dc = S.put(cs);
   for (int jb = 0; jb < Mmax; jb += 64) {
     hipLaunchKernelGGL(k_potrf_tile, dim3((unsigned)cs.size()), dim3(64), 0, st, dc, jb);
-    LC(hipGetLastError());
+    HC(hipGetLastError());
     std::vector<Gemm> pan, upd;
     for (const Chol& c : cs) {
       if (c.M <= jb + 64) continue;
@@ -1601,7 +1595,7 @@ void eigh(Stager& S, hipStream_t st, const std::vector<Eigh>& es, const std::fun
       const int next = i + 1 < TNB && p + i + 1 < Mmax - 1;
       hipLaunchKernelGGL(k_sy_w, dim3(n, nsw), dim3(SW_T), 0, st, de, p, i, ns, next);
     }
-    LC(hipGetLastError());
+    HC(hipGetLastError());
     std::vector<Gemm> g1, g2;
     for (const Eigh& e : es) {
       const int nb = std::min(TNB, e.M - 1 - p), q0 = p + nb, L = e.M - q0;
@@ -1617,16 +1611,16 @@ void eigh(Stager& S, hipStream_t st, const std::vector<Eigh>& es, const std::fun
     gemm(S, st, false, true, g2);
   }
   hipLaunchKernelGGL(k_sytrd_last, dim3(n), dim3(64), 0, st, de);
-  LC(hipGetLastError());
+  HC(hipGetLastError());
   phase(1);
   const size_t lds_st = (3 * (size_t)Mmax + 64) * sizeof(double);  // d | e2 | red[64] | e (k_stein)
   const unsigned nst = (unsigned)((Mmax + ST_T - 1) / ST_T), nto = (unsigned)((Mmax + 63) / 64);
   hipLaunchKernelGGL(k_stebz, dim3(n, nst), dim3(ST_T), lds_st, st, de);
-  LC(hipGetLastError());
+  HC(hipGetLastError());
   hipLaunchKernelGGL(k_stein, dim3(n, nst), dim3(ST_T), lds_st, st, de);
-  LC(hipGetLastError());
+  HC(hipGetLastError());
   hipLaunchKernelGGL(k_stein_out, dim3(n, nto * nto), dim3(256), 0, st, de);
-  LC(hipGetLastError());
+  HC(hipGetLastError());
   phase(2);
   // BCGS2 over blocks of `ob` eigenvectors (columns of Z = E.A): a block is
   // projected out of every earlier block twice (two wide products per pass,
@@ -1662,9 +1656,9 @@ void eigh(Stager& S, hipStream_t st, const std::vector<Eigh>& es, const std::fun
     for (int p = P; p < std::min(P + ob, Mmax); p += TNB) {
       if (p > P) project(P, p, TNB);
       hipLaunchKernelGGL(k_orth_panel, dim3(n), dim3(MG_T), 0, st, de, p);
-      LC(hipGetLastError());
+      HC(hipGetLastError());
       hipLaunchKernelGGL(k_mgs_panel, dim3(n), dim3(MG_T), 0, st, de, p);
-      LC(hipGetLastError());
+      HC(hipGetLastError());
     }
   }
   // back-transform: Z <- (I - V_p T_p V_p') Z for the panels in reverse order
@@ -1690,7 +1684,7 @@ void eigh(Stager& S, hipStream_t st, const std::vector<Eigh>& es, const std::fun
     gemm(S, st, false, false, g3);
   }
   hipLaunchKernelGGL(k_reverse_cols, dim3(n, 64), dim3(256), 0, st, de);
-  LC(hipGetLastError());
+  HC(hipGetLastError());
   phase(4);
 }
 

@@ -5,36 +5,30 @@
 // part of include/oi.h.
 #include <hip/hip_runtime.h>
 
-#include <exception>
 #include <string>
 #include <vector>
 
-#include "../../include/oi.h"
+#include "oi_host.h"
 #include "oi_linalg.h"
-
-extern "C" int oi_set_last_error(int code, const char* msg);
 
 namespace {
 
+// oi_guarded's mapping with the routine's name in front of the text; the
+// stream is drained before the descriptor ring is destroyed
 template <class F>
 int guarded(void* stream, const char* what, F&& run) {
-  try {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    oila::Stager S;  // outlives the launches: the stream is drained before it is destroyed
-    S.bind(st);
-    int rc = 0;
-    try {
-      run(S, st);
-    } catch (const oila::LinalgErr& e) {
-      rc = oi_set_last_error(OI_E_HIP, (std::string(what) + ": " + e.msg).c_str());
-    }
-    const hipError_t err = hipStreamSynchronize(st);
-    if (rc == 0 && err != hipSuccess)
-      rc = oi_set_last_error(OI_E_HIP, (std::string(what) + ": " + hipGetErrorString(err)).c_str());
-    return rc;
-  } catch (const std::exception& e) {
-    return oi_set_last_error(OI_E_HIP, (std::string(what) + ": " + e.what()).c_str());
-  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  oila::Stager S;
+  S.bind(st);
+  int rc = oi_guarded([&] {
+    run(S, st);
+    return 0;
+  });
+  if (rc) rc = oi_set_last_error(rc, (std::string(what) + ": " + oi_last_error()).c_str());
+  const hipError_t err = hipStreamSynchronize(st);
+  if (rc == 0 && err != hipSuccess)
+    rc = oi_set_last_error(OI_E_HIP, (std::string(what) + ": " + hipGetErrorString(err)).c_str());
+  return rc;
 }
 
 template <class T>

@@ -31,8 +31,9 @@
 // is a hand-written gfx950 kernel of oi_linalg.hip (no LAPACK / rocSOLVER /
 // rocBLAS): the eigensolver is one workgroup per matrix for the Householder
 // tridiagonalisation and the tridiagonal eigenpairs, batched MFMA products for
-// the orthogonalisation and the back-transform.  Cells of a call are dealt
-// over LANES (own stream and workspace); per-cell status comes back in one
+// the orthogonalisation and the back-transform.  A Runner evaluates a chunk
+// of cells phase by phase on one stream; independent Runners (the groups of a
+// fit) overlap on streams of their own.  Per-cell status comes back in one
 // copy at the end.
 #include <hip/hip_runtime.h>
 
@@ -45,19 +46,14 @@
 #include <string>
 #include <vector>
 
-#include "../../include/oi.h"
 #include "oi_gemm.h"
+#include "oi_host.h"
 #include "oi_linalg.h"
+#include "oi_matern.h"
 
 #pragma clang fp contract(off)
 
-extern "C" int oi_set_last_error(int code, const char* msg);  // oi_engine.cpp
-extern "C" void oi_profile_add(const char* name, int64_t launches, double ms, double flops,
-                               double bytes);  // oi_engine.cpp
-
 namespace {
-
-constexpr double SQRT3 = 1.7320508075688772;  // np.sqrt(3.)
 
 // ---------------------------------------------------------------- kernels --
 
@@ -71,14 +67,13 @@ __global__ void k_nys_scale(const double* __restrict__ x, int64_t n, double l0, 
   const double ell[3] = {l0, l1, l2};
   for (int d = 0; d < 3; ++d) {
     const double v = x[i * 3 + d];
-    sc[i * 3 + d] = (SQRT3 * v) / ell[d];
-    if (sq) sq[i * 3 + d] = SQRT3 * (v / ell[d]);
+    sc[i * 3 + d] = matern_scale(v, ell[d]);
+    if (sq) sq[i * 3 + d] = matern_scale_q(v, ell[d]);
   }
 }
 
 __device__ inline double dist3(const double* a, const double* b) {
-  const double d0 = a[0] - b[0], d1 = a[1] - b[1], d2 = a[2] - b[2];
-  return sqrt(d0 * d0 + d1 * d1 + d2 * d2);  // scipy pdist/cdist 'euclidean'
+  return matern_dist(a[0] - b[0], a[1] - b[1], a[2] - b[2]);
 }
 
 // out[i + ld j] = sf2 (1 + Q) exp(-Q), Q = |sa[ia[i]] - sb[ib[j]]| (column-major)
@@ -90,8 +85,9 @@ __global__ void k_nys_cross(const double* __restrict__ sa, const int64_t* __rest
   const int64_t j = blockIdx.y;
   if (i >= na) return;
   const int64_t ra = ia ? ia[i] : i, rb = ib ? ib[j] : j;
-  const double Q = dist3(sa + ra * 3, sb + rb * 3);
-  out[i + ld * j] = sf2 * ((1.0 + Q) * exp(-Q));
+  const double* a = sa + ra * 3;
+  const double* b = sb + rb * 3;
+  out[i + ld * j] = matern32(sf2, a[0] - b[0], a[1] - b[1], a[2] - b[2]);
 }
 
 // s[s <= 0] = 1e-12; st = n * s / M  for the M real eigenvalues; st = 1 on a
@@ -334,17 +330,6 @@ __global__ void __launch_bounds__(256) k_nys_grad_mfma(const double* __restrict_
 
 // ------------------------------------------------------------------- host --
 
-struct HipErr {
-  std::string msg;
-};
-
-#define HC(expr)                                                                              \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess) throw HipErr{std::string(#expr) + ": " + hipGetErrorString(e_)};    \
-  } while (0)
-#define KCHK() HC(hipGetLastError())
-
 // opts.profile: HIP events around each stage of each cell, summed per stage
 // into oi_profile_json (algorithmic flops / bytes per stage alongside)
 enum { S_BUILD, S_EIGH, S_EIGH_VEC, S_EIGH_ORTH, S_EIGH_BACK, S_PANEL, S_KI, S_APPLY, S_LOGDET, S_GRAD,
@@ -354,55 +339,6 @@ enum { S_BUILD, S_EIGH, S_EIGH_VEC, S_EIGH_ORTH, S_EIGH_BACK, S_PANEL, S_KI, S_A
 const char* kStage[S_COUNT] = {"nys_build",  "nys_eigh",   "nys_eigh_vectors", "nys_eigh_orth",
                                "nys_eigh_back", "nys_panels", "nys_ki_gemm", "nys_apply",
                                "nys_logdet", "nys_grad",   "nys_predict"};
-struct Stager {
-  bool on = false;
-  hipStream_t st = nullptr;
-  std::vector<hipEvent_t> ev;
-  std::vector<int> kind;
-  std::vector<double> fl, by;
-  void begin(int k, double flops, double bytes) {
-    if (!on) return;
-    kind.push_back(k);
-    fl.push_back(flops);
-    by.push_back(bytes);
-    rec();
-  }
-  void end() {
-    if (on) rec();
-  }
-  void rec() {
-    hipEvent_t e;
-    HC(hipEventCreate(&e));
-    ev.push_back(e);
-    HC(hipEventRecord(e, st));
-  }
-  void flush() {  // after the stream has been synchronised
-    if (!on) return;
-    double ms[S_COUNT] = {}, f[S_COUNT] = {}, b[S_COUNT] = {};
-    int64_t n[S_COUNT] = {};
-    for (size_t q = 0; q < kind.size(); ++q) {
-      float t = 0.f;
-      HC(hipEventElapsedTime(&t, ev[2 * q], ev[2 * q + 1]));
-      ms[kind[q]] += t;
-      f[kind[q]] += fl[q];
-      b[kind[q]] += by[q];
-      n[kind[q]] += 1;
-    }
-    for (int k = 0; k < S_COUNT; ++k)
-      if (n[k]) oi_profile_add(kStage[k], n[k], ms[k], f[k], b[k]);
-    for (auto e : ev) (void)hipEventDestroy(e);
-    ev.clear();
-    kind.clear();
-    fl.clear();
-    by.clear();
-  }
-  ~Stager() {
-    for (auto e : ev) (void)hipEventDestroy(e);
-  }
-};
-
-inline unsigned blocks(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
 // per-cell device results: [r.A, sum log diag(L) + sum log st / 2, g0..g4 raw
 // sums, k*.A, |k*|^2, |W k*|^2]
 constexpr int NRES = 10;
@@ -442,17 +378,6 @@ int check_batch(Batch& b) {
   return 0;
 }
 
-int setup(const oi_options* opts, oi_options& o) {
-  oi_options_default(&o);
-  if (opts) o = *opts;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return oi_set_last_error(OI_E_NODEV, "no HIP device available");
-  if (o.device < 0 || o.device >= ndev) return oi_set_last_error(OI_E_ARG, "bad device ordinal");
-  if (hipSetDevice(o.device) != hipSuccess) return oi_set_last_error(OI_E_HIP, "hipSetDevice failed");
-  return 0;
-}
-
 // One cell's inputs on the device: the row of the cell table a Runner reads.
 struct CellSrc {
   const double* x;     // n x 3
@@ -462,37 +387,10 @@ struct CellSrc {
   int64_t n, M;
 };
 
-struct Buf;
 // Outcome of one cell at one hyper point (host side).
 struct CellOut {
   double nlz, grad[5], fs, sd, sprior;
   int status;
-};
-
-// Device buffer; stream-ordered (hipMallocAsync / hipFreeAsync on `st`) when
-// given a stream, so freeing it never waits for the whole device.
-struct Buf {
-  void* p = nullptr;
-  hipStream_t st = nullptr;
-  bool async = false;
-  Buf() = default;
-  Buf(const Buf&) = delete;
-  Buf& operator=(const Buf&) = delete;
-  void alloc(size_t bytes) {
-    if (bytes) HC(hipMalloc(&p, bytes));
-  }
-  void alloc_async(size_t bytes, hipStream_t s) {
-    st = s;
-    async = true;
-    if (bytes) HC(hipMallocAsync(&p, bytes, s));
-  }
-  ~Buf() {
-    if (p) (void)(async ? hipFreeAsync(p, st) : hipFree(p));
-  }
-  template <class T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
 };
 
 // Device copy of one validated batch (inputs when they came from the host,
@@ -501,7 +399,7 @@ struct Buf {
 // returns once the copies are done) and freed on it: a session orders `st`
 // after every group's last use before dropping a batch.
 struct BatchDev {
-  Buf hx, hy, dsel, dxs;
+  DevBuf hx, hy, dsel, dxs;
   std::vector<CellSrc> rows;
   BatchDev(const Batch& b, const double* xs, bool device_inputs, hipStream_t st) {
     const int64_t N = b.offs[b.ncell], S = b.soffs[b.ncell];
@@ -537,44 +435,6 @@ inline bool fused_objective() {
   return !(e && atoi(e) == 0);
 }
 
-struct Lane {
-  hipStream_t st = nullptr;
-  oila::Stager la;  // launch descriptors of the oila kernels on this lane's stream
-  Buf Knm, U1, ut, Ki, Wp, Av, tv, ks, kv, xsc, part;
-  Stager sg;
-  hipEvent_t done = nullptr;
-  Lane(int64_t nmax, int64_t mmax, bool obj, bool pred, bool profile) {
-    HC(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    HC(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-    la.bind(st);
-    const int64_t nM = nmax * mmax, nt = blocks(nmax, 64);
-    Knm.alloc(nM * 8);
-    U1.alloc(nM * 8);
-    ut.alloc(nM * 8);
-    Av.alloc(nmax * 8);
-    tv.alloc(mmax * 8);
-    if (obj) {
-      if (fused_objective()) {
-        Wp.alloc((size_t)blocks(mmax, 64) * nt * 4096 * 8);
-      } else {
-        Ki.alloc(nmax * nmax * 8);
-      }
-      part.alloc(nt * nt * 5 * 8);
-    }
-    if (pred) {
-      ks.alloc(nmax * 8);
-      kv.alloc(mmax * 8);
-      xsc.alloc(3 * 8);
-    }
-    sg.on = profile;
-    sg.st = st;
-  }
-  ~Lane() {
-    if (done) (void)hipEventDestroy(done);
-    if (st) (void)hipStreamDestroy(st);
-  }
-};
-
 // Evaluates any subset of a validated batch's cells at given LINEAR hypers.
 //
 // The eigensolver runs one workgroup per matrix and the blocked Cholesky one
@@ -583,10 +443,10 @@ struct Lane {
 // equal-padded-M group, (3) the n x M panels and B of every cell, (4) one
 // batched Cholesky per group, (5) the triangular solve, objective and
 // prediction of every cell.
-// Per-cell phases are dealt round-robin over LANES (OI_NYS_LANES, default 1:
-// stream + oila::gemm descriptor ring + scratch each; more lanes measured no faster with
-// the box's 4 hardware queues); per-slot state (scaled inputs,
-// K_mm -> u, s, st, C, B -> L) lives in chunk-sized slot arrays.
+// Everything is launched on the Runner's one stream; what overlaps is the
+// Runners of different groups.  Per-slot state (scaled inputs, K_mm -> u, s,
+// st, K_nm, U1 -> ut, C, B -> L) lives in chunk-sized slot arrays; the
+// per-cell scratch of phase 5 is reused from cell to cell in stream order.
 class Runner {
  public:
   // Reads cells from *tab (rows indexed by cell id; the table may grow between
@@ -608,27 +468,35 @@ class Runner {
     la_.bind(st_);
     sg_.on = o.profile != 0;
     sg_.st = st_;
-    int nl = 1;
-    if (const char* e = getenv("OI_NYS_LANES")) nl = atoi(e);
-    nl = nl < 1 ? 1 : nl;
-    nl = nl > cap ? (int)cap : nl;
-    for (int l = 0; l < nl; ++l)
-      lanes_.emplace_back(new Lane(nmax, mmax, want_obj, want_pred, o.profile != 0));
+    // phase 5's per-cell scratch
+    const int64_t nt = blocks(nmax, 64);
+    Av_.alloc(nmax * 8);
+    tv_.alloc(mmax * 8);
+    if (want_obj) {
+      if (fused_objective()) {
+        Wp_.alloc((size_t)blocks(mmax, 64) * nt * 4096 * 8);
+      } else {
+        Ki_.alloc(nmax * nmax * 8);
+      }
+      part_.alloc(nt * nt * 5 * 8);
+    }
+    if (want_pred) {
+      ks_.alloc(nmax * 8);
+      kv_.alloc(mmax * 8);
+      xsc_.alloc(3 * 8);
+    }
     // padding quantum (OI_NYS_PAD, default 32; 0 = no padding): K_mm and B of a
     // cell are factored as diag(A, d I) of size Mp = M rounded up (the slot
     // strides of the chunk arrays; results equal the unpadded path to rounding)
     if (const char* e = getenv("OI_NYS_PAD")) padq_ = std::max(0, atoi(e));
     mpmax_ = Mp(mmax);
-    // slot arrays: sc, sq (n x 3), Kmm (Mp^2), s, st (Mp), C (n x M), B (Mp^2),
+    // slot arrays: sc, sq (n x 3), Kmm (Mp^2), s, st (Mp), C, Knm, U1 (n x M), B (Mp^2),
     // the eigensolver's workspace, the Cholesky's diagonal-block inverses;
     // chunk <= 64 cells and <= 1/4 of the free HBM
     const int64_t mmaxp = mpmax_;
     ewd_ = oila::eigh_workspace_doubles((int)mmaxp);
     nd64_ = (mmaxp + 63) / 64;
-    // OI_NYS_B3 (default 1): phase 3's two n x M products batched over the
-    // chunk (per-slot K_nm and U1 / ut) instead of one cell at a time per lane
-    if (const char* e = getenv("OI_NYS_B3")) b3_ = atoi(e) != 0;
-    const size_t per = (size_t)(6 * nmax + 2 * mmaxp * mmaxp + 2 * mmaxp + (b3_ ? 3 : 1) * nmax * mmaxp) * 8 +
+    const size_t per = (size_t)(6 * nmax + 2 * mmaxp * mmaxp + 2 * mmaxp + 3 * nmax * mmaxp) * 8 +
                        (ewd_ + (size_t)nd64_ * 4096) * 8;
     size_t fr = 0, tot = 0;
     HC(hipMemGetInfo(&fr, &tot));
@@ -641,19 +509,14 @@ class Runner {
     eval_.alloc(ch * mmaxp * 8);
     stl_.alloc(ch * mmaxp * 8);
     C_.alloc(ch * nmax * mmaxp * 8);
-    if (b3_) {
-      Knm_.alloc(ch * nmax * mmaxp * 8);
-      U1_.alloc(ch * nmax * mmaxp * 8);
-    }
+    Knm_.alloc(ch * nmax * mmaxp * 8);
+    U1_.alloc(ch * nmax * mmaxp * 8);
     B_.alloc(ch * mmaxp * mmaxp * 8);
     EW_.alloc(ch * ewd_ * 8);
     Dinv_.alloc(ch * nd64_ * 4096 * 8);
-    HC(hipEventCreateWithFlags(&ready_, hipEventDisableTiming));
   }
   ~Runner() {
     if (own_ && st_) (void)hipStreamSynchronize(st_);
-    for (Lane* l : lanes_) delete l;
-    if (ready_) (void)hipEventDestroy(ready_);
     if (hr_) (void)hipHostFree(hr_);
     if (hi_) (void)hipHostFree(hi_);
     if (own_ && st_) (void)hipStreamDestroy(st_);
@@ -692,14 +555,11 @@ class Runner {
     HC(hipMemsetAsync(info_.p, 0, nc * NINFO * sizeof(int32_t), st_));
     for (int64_t p0 = 0; p0 < nc; p0 += chunk_) {
       const int64_t p1 = std::min(nc, p0 + chunk_);
-      lanes_phase(p0, p1, 1);
+      for (int64_t p = p0; p < p1; ++p) phase1(p, p - p0);
       batched(p0, p1, 0);
-      if (b3_)
-        batched3(p0, p1);
-      else
-        lanes_phase(p0, p1, 3);
+      batched3(p0, p1);
       batched(p0, p1, 1);
-      lanes_phase(p0, p1, 5);
+      for (int64_t p = p0; p < p1; ++p) phase5(p, p - p0);
     }
     HC(hipMemcpyAsync(hr_, res_.p, nc * NRES * 8, hipMemcpyDeviceToHost, st_));
     HC(hipMemcpyAsync(hi_, info_.p, nc * NINFO * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
@@ -714,9 +574,7 @@ class Runner {
     const double mean = mean_;
     HC(hipStreamSynchronize(st_));
     sg_.flush();
-    for (Lane* l : lanes_) l->sg.flush();
     la_.reset();  // every launch that read the staged descriptors has completed
-    for (Lane* l : lanes_) l->la.reset();
     const double inf = INFINITY, nan = NAN;
     for (int64_t p = 0; p < nc; ++p) {
       const int64_t k = order_[p], c = cells[k];
@@ -755,24 +613,6 @@ class Runner {
   int64_t Mof(int64_t c) const { return (*tab_)[c].M; }
   int64_t Mp(int64_t M) const { return padq_ > 0 ? (M + padq_ - 1) / padq_ * padq_ : M; }
 
-  // per-cell phase `ph` for positions [p0, p1) dealt over the lanes, fenced
-  // against the main stream on both sides
-  void lanes_phase(int64_t p0, int64_t p1, int ph) {
-    const int64_t nl = std::min<int64_t>((int64_t)lanes_.size(), p1 - p0);
-    HC(hipEventRecord(ready_, st_));
-    for (int64_t l = 0; l < nl; ++l) HC(hipStreamWaitEvent(lanes_[l]->st, ready_, 0));
-    for (int64_t p = p0; p < p1; ++p) {
-      Lane& L = *lanes_[(p - p0) % nl];
-      if (ph == 1) phase1(L, p, p - p0);
-      else if (ph == 3) phase3(L, p, p - p0);
-      else phase5(L, p, p - p0);
-    }
-    for (int64_t l = 0; l < nl; ++l) {
-      HC(hipEventRecord(lanes_[l]->done, lanes_[l]->st));
-      HC(hipStreamWaitEvent(st_, lanes_[l]->done, 0));
-    }
-  }
-
   // which = 0: s, u = eigh(Kmm) (oila::eigh; u overwrites Kmm); 1: L = chol(B)
   // (oila::cholesky, in place, with the diagonal-block inverses kept for the
   // triangular solve) -- one batched call per run of slots with equal padded
@@ -802,8 +642,8 @@ class Runner {
           if (k < 4) sg_.begin(kind[k], fl[k], 0.0);
         });
       } else {
-        // L = chol(B); half log-determinants (the lanes then form W' = C L^-T
-        // by a block triangular solve with the kept diagonal-block inverses)
+        // L = chol(B); half log-determinants; then W' = C L^-T by a block
+        // triangular solve with the kept diagonal-block inverses
         sg_.begin(S_PANEL, dM * dM * dM / 3 * cnt, 0.0);
         double* B0 = B_.as<double>() + s0 * mm;
         std::vector<oila::Chol> cs;
@@ -811,7 +651,7 @@ class Runner {
           cs.push_back(oila::Chol{B0 + q * mm, Dinv_.as<double>() + (s0 + q) * nd64_ * 4096,
                                   info_.as<int32_t>() + (g0 + q) * NINFO + 1, iM, iM});
         oila::cholesky(la_, st_, cs);
-        // the pad block is the identity: log 1 = 0 and st is 1 there (see phase3)
+        // the pad block is the identity: log 1 = 0 and st is 1 there (see batched3)
         hipLaunchKernelGGL(k_nys_logdet, dim3(cnt), dim3(256), 0, st_, B0, M, M, mm,
                            stl_.as<double>() + s0 * mpmax_, mpmax_,
                            res_.as<double>() + g0 * NRES, (int64_t)NRES);
@@ -869,7 +709,8 @@ class Runner {
     return R;
   }
 
-  // phase 3 for a whole chunk on the main stream: the per-cell elementwise
+  // phase 3 for a whole chunk: s clamp, st; Knm = SGPkernel(x, xs=x[sel]);
+  // U1 = Knm u; ut, C = Vi ut; B = diag(1/st) + ut' C -- the per-cell elementwise
   // kernels, and each of the two n x M products as ONE batched oila::gemm over
   // the chunk's cells (per-cell launches of ~1 000 64 x 64 tiles left the
   // chip under-filled in the last wave of tiles)
@@ -921,10 +762,10 @@ class Runner {
   }
 
   // scaled inputs, Kmm (NB1 Nystroem: SGPkernel(x[sel]))
-  void phase1(Lane& L, int64_t p, int64_t slot) {
+  void phase1(int64_t p, int64_t slot) {
     const CellRefs R = refs(p, slot);
-    hipStream_t st = L.st;
-    L.sg.begin(S_BUILD, 0.0, 8.0 * R.dM * R.dM);
+    hipStream_t st = st_;
+    sg_.begin(S_BUILD, 0.0, 8.0 * R.dM * R.dM);
     hipLaunchKernelGGL(k_nys_scale, dim3(blocks(R.n, 256)), dim3(256), 0, st, R.x, R.n, R.hp[0],
                        R.hp[1], R.hp[2], R.sc, obj_ ? R.sq : nullptr);
     KCHK();
@@ -938,60 +779,27 @@ class Runner {
                          R.Kmm, R.M, R.Mp, 2.0 * R.dM * R.hp[3] + 1.0);
       KCHK();
     }
-    L.sg.end();
-  }
-
-  // s clamp, st; Knm = SGPkernel(x, xs=x[sel]); U1 = Knm u; ut, C = Vi ut;
-  // B = diag(1/st) + ut' C
-  void phase3(Lane& L, int64_t p, int64_t slot) {
-    const CellRefs R = refs(p, slot);
-    hipStream_t st = L.st;
-    double* Knm = L.Knm.as<double>();
-    double* U1 = L.U1.as<double>();
-    double* ut = L.ut.as<double>();
-    L.sg.begin(S_PANEL, 4 * R.dn * R.dM * R.dM, 8.0 * R.dn * R.dM);
-    hipLaunchKernelGGL(k_nys_eigpost, dim3(blocks(R.Mp, 256)), dim3(256), 0, st, R.s, R.M, R.Mp,
-                       R.n, R.stl);
-    KCHK();
-    hipLaunchKernelGGL(k_nys_cross, dim3(blocks(R.n, 256), (unsigned)R.M), dim3(256), 0, st, R.sc,
-                       nullptr, R.n, R.sc, R.sl, R.hp[3], Knm, R.n);
-    KCHK();
-    // U1 = Knm u
-    oila::gemm(L.la, st, false, false, {oila::Gemm{Knm, R.Kmm, U1, R.in, R.iM, R.iM, R.in, R.iMp, R.in, 1.0, 0.0, 0}});
-    hipLaunchKernelGGL(k_nys_ut, dim3(blocks(R.n * R.M, 256)), dim3(256), 0, st, U1, R.n, R.M, R.s,
-                       std::sqrt(R.dM / R.dn), 1.0 / R.hp[4], ut, R.C);
-    KCHK();
-    // B = ut' C (then + diag(1/st))
-    oila::gemm(L.la, st, true, false, {oila::Gemm{ut, R.C, R.B, R.iM, R.iM, R.in, R.in, R.in, R.iMp, 1.0, 0.0, 0}});
-    hipLaunchKernelGGL(k_nys_diag, dim3(blocks(R.M, 256)), dim3(256), 0, st, R.B, R.M, R.Mp, R.stl, 1,
-                       0.0);
-    KCHK();
-    if (R.Mp > R.M) {
-      hipLaunchKernelGGL(k_nys_pad, dim3(blocks(R.Mp, 256), (unsigned)R.Mp), dim3(256), 0, st, R.B,
-                         R.M, R.Mp, 1.0);
-      KCHK();
-    }
-    L.sg.end();
+    sg_.end();
   }
 
   // W' = C L^-T;  A = r/sn2 - W'(W r);  objective (Ki, fused pass);  predict
-  void phase5(Lane& L, int64_t p, int64_t slot) {
+  void phase5(int64_t p, int64_t slot) {
     const CellRefs R = refs(p, slot);
-    hipStream_t st = L.st;
+    hipStream_t st = st_;
     const double sf2 = R.hp[3], isn2 = 1.0 / R.hp[4];
     const double dn = R.dn, dM = R.dM;
     double* Wt = R.C;  // n x M: W' = C L^-T, formed in place by batched()
-    double* Av = L.Av.as<double>();
-    double* tv = L.tv.as<double>();
-    Stager& sg = L.sg;
+    double* Av = Av_.as<double>();
+    double* tv = tv_.as<double>();
+    StageTimer& sg = sg_;
     sg.begin(S_APPLY, 2.0 * dM * dM * dn + 4.0 * dn * dM, 16.0 * dn * dM);
     hipLaunchKernelGGL(k_nys_vi, dim3(blocks(R.n, 256)), dim3(256), 0, st, R.r, R.n, isn2, Av);
     KCHK();
-    oila::gemv(L.la, st, true, {oila::Gemv{Wt, R.r, tv, R.in, R.iM, R.in, 1.0, 0.0}});     // tv = W r
-    oila::gemv(L.la, st, false, {oila::Gemv{Wt, tv, Av, R.in, R.iM, R.in, -1.0, 1.0}});   // A -= W' tv
+    oila::gemv(la_, st, true, {oila::Gemv{Wt, R.r, tv, R.in, R.iM, R.in, 1.0, 0.0}});     // tv = W r
+    oila::gemv(la_, st, false, {oila::Gemv{Wt, tv, Av, R.in, R.iM, R.in, -1.0, 1.0}});   // A -= W' tv
     sg.end();
     if (obj_) {
-      double* Ki = L.Ki.as<double>();
+      double* Ki = Ki_.as<double>();
       sg.begin(S_LOGDET, 2.0 * dn, 16.0 * dn);
       hipLaunchKernelGGL(k_nys_dot, dim3(1), dim3(256), 0, st, R.r, Av, R.n, R.rs + 0);
       KCHK();
@@ -1002,15 +810,15 @@ class Runner {
         const int ntri = Tn * (Tn + 1) / 2;
         sg.begin(S_KI, dn * dn * dM, 8.0 * dn * dM);
         hipLaunchKernelGGL(k_nys_pack, dim3((unsigned)(Tn * Tk)), dim3(256), 0, st, Wt, R.n, R.M,
-                           Tn, L.Wp.as<double>());
+                           Tn, Wp_.as<double>());
         KCHK();
         sg.end();
         sg.begin(S_GRAD, dn * dn * dM, 0.0);
         hipLaunchKernelGGL(k_nys_grad_mfma, dim3((unsigned)ntri), dim3(256), 0, st,
-                           L.Wp.as<double>(), Tn, Tk, Av, R.sc, R.sq, R.n, sf2, isn2,
-                           L.part.as<double>());
+                           Wp_.as<double>(), Tn, Tk, Av, R.sc, R.sq, R.n, sf2, isn2,
+                           part_.as<double>());
         KCHK();
-        hipLaunchKernelGGL(k_nys_partsum, dim3(1), dim3(256), 0, st, L.part.as<double>(),
+        hipLaunchKernelGGL(k_nys_partsum, dim3(1), dim3(256), 0, st, part_.as<double>(),
                            (int64_t)ntri, R.rs + 2);
         KCHK();
         sg.end();
@@ -1018,7 +826,7 @@ class Runner {
         // Ki = Vi - W'W (OI_NYS_FUSED=0 only: one full oila::gemm product; the
         // sweep below reads the lower half)
         sg.begin(S_KI, 2.0 * dn * dn * dM, 8.0 * dn * dn);
-        oila::gemm(L.la, st, false, true, {oila::Gemm{Wt, Wt, Ki, R.in, R.in, R.iM, R.in, R.in, R.in, -1.0, 0.0, 0}});
+        oila::gemm(la_, st, false, true, {oila::Gemm{Wt, Wt, Ki, R.in, R.in, R.iM, R.in, R.in, R.in, -1.0, 0.0, 0}});
         hipLaunchKernelGGL(k_nys_diag, dim3(blocks(R.n, 256)), dim3(256), 0, st, Ki, R.n, R.n, nullptr,
                            0, isn2);
         KCHK();
@@ -1027,9 +835,9 @@ class Runner {
         sg.begin(S_GRAD, 0.0, 4.0 * dn * dn);
         const unsigned nt = blocks(R.n, 64);
         hipLaunchKernelGGL(k_nys_grad, dim3(nt, nt), dim3(256), 0, st, Ki, Av, R.sc, R.sq, R.n, sf2,
-                           L.part.as<double>());
+                           part_.as<double>());
         KCHK();
-        hipLaunchKernelGGL(k_nys_partsum, dim3(1), dim3(256), 0, st, L.part.as<double>(),
+        hipLaunchKernelGGL(k_nys_partsum, dim3(1), dim3(256), 0, st, part_.as<double>(),
                            (int64_t)nt * nt, R.rs + 2);
         KCHK();
         sg.end();
@@ -1038,19 +846,19 @@ class Runner {
     if (pred_) {
       // k* = SGPkernel(x, xs=xs); fs = mean + k*.A; k*'Ki k* = |k*|^2/sn2 - |W k*|^2
       sg.begin(S_PRED, 2.0 * dn * dM, 8.0 * dn * dM);
-      double* ks = L.ks.as<double>();
-      double* kv = L.kv.as<double>();
+      double* ks = ks_.as<double>();
+      double* kv = kv_.as<double>();
       hipLaunchKernelGGL(k_nys_scale, dim3(1), dim3(64), 0, st, (*tab_)[R.c].xs,
-                         (int64_t)1, R.hp[0], R.hp[1], R.hp[2], L.xsc.as<double>(), nullptr);
+                         (int64_t)1, R.hp[0], R.hp[1], R.hp[2], xsc_.as<double>(), nullptr);
       KCHK();
       hipLaunchKernelGGL(k_nys_cross, dim3(blocks(R.n, 256), 1), dim3(256), 0, st, R.sc, nullptr,
-                         R.n, L.xsc.as<double>(), nullptr, sf2, ks, R.n);
+                         R.n, xsc_.as<double>(), nullptr, sf2, ks, R.n);
       KCHK();
       hipLaunchKernelGGL(k_nys_dot, dim3(1), dim3(256), 0, st, ks, Av, R.n, R.rs + 7);
       KCHK();
       hipLaunchKernelGGL(k_nys_dot, dim3(1), dim3(256), 0, st, ks, ks, R.n, R.rs + 8);
       KCHK();
-      oila::gemv(L.la, st, true, {oila::Gemv{Wt, ks, kv, R.in, R.iM, R.in, 1.0, 0.0}});  // kv = W k*
+      oila::gemv(la_, st, true, {oila::Gemv{Wt, ks, kv, R.in, R.iM, R.in, 1.0, 0.0}});  // kv = W k*
       hipLaunchKernelGGL(k_nys_dot, dim3(1), dim3(256), 0, st, kv, kv, R.M, R.rs + 9);
       KCHK();
       sg.end();
@@ -1061,18 +869,16 @@ class Runner {
   int64_t nmax_ = 0, cap_ = 0;
   hipStream_t st_;
   bool obj_ = false, pred_ = false, alloc_obj_, alloc_pred_;
-  Buf res_, info_;
-  Buf sc_, sq_, Kmm_, eval_, stl_, C_, B_, EW_, Dinv_, Knm_, U1_;
-  bool b3_ = true;
+  DevBuf res_, info_;
+  DevBuf sc_, sq_, Kmm_, eval_, stl_, C_, B_, EW_, Dinv_, Knm_, U1_;  // chunk-sized slot arrays
+  DevBuf Av_, tv_, Wp_, Ki_, part_, ks_, kv_, xsc_;                   // per-cell scratch
   int64_t chunk_ = 1;
   int padq_ = 32;
   int64_t mpmax_ = 0;
   size_t ewd_ = 0;
   int64_t nd64_ = 0;
   oila::Stager la_;
-  Stager sg_;
-  std::vector<Lane*> lanes_;
-  hipEvent_t ready_ = nullptr;
+  StageTimer sg_{kStage, S_COUNT};
   const std::vector<int64_t>* cells_ = nullptr;
   const double* hyp_ = nullptr;
   std::vector<int64_t> order_;
@@ -1085,17 +891,54 @@ class Runner {
   int32_t* hi_ = nullptr;
 };
 
-template <class F>
-int guarded(F&& f) {
-  try {
-    return f();
-  } catch (const HipErr& e) {
-    return oi_set_last_error(OI_E_HIP, e.msg.c_str());
-  } catch (const oila::LinalgErr& e) {
-    return oi_set_last_error(OI_E_HIP, e.msg.c_str());
-  } catch (const std::bad_alloc&) {
-    return oi_set_last_error(OI_E_NOMEM, "allocation failed");
+// ---- the steps of one cell's fit (NB1 SMLII + scipy CG), shared by the
+// one-shot fit and the session
+
+// A cell's restated scipy CG at x0 (6-slot; the sixth gradient is 0, which
+// leaves scipy's iteration unchanged) and its first requested point (req, 6).
+// Returns whether the cell wants an evaluation.
+bool cg_start(oi_cg*& cg, const double* x0, double gtol, int32_t maxiter, double* req) {
+  const double x6[6] = {x0[0], x0[1], x0[2], x0[3], x0[4], 0.0};
+  cg = oi_cg_create(x6, gtol, maxiter);
+  if (!cg) throw std::bad_alloc();
+  const int rc = oi_cg_step(cg, req);
+  if (rc < 0) throw HipErr{"oi_cg_step failed"};
+  return rc == 1;
+}
+
+// Feeds one evaluation to the cell's CG; the next requested point into req.
+// Returns whether the cell wants another evaluation.
+bool cg_advance(oi_cg* cg, const CellOut& r, double* req) {
+  const double g6[6] = {r.grad[0], r.grad[1], r.grad[2], r.grad[3], r.grad[4], 0.0};
+  if (oi_cg_feed(cg, r.nlz, g6) != 0) throw HipErr{"oi_cg_feed failed"};
+  const int rc = oi_cg_step(cg, req);
+  if (rc < 0) throw HipErr{"oi_cg_step failed"};
+  return rc == 1;
+}
+
+// The fitted LINEAR hypers (5) of a finished cell; info[4] = (nit, status,
+// nfev, nobj) when asked for.
+void cg_readout(oi_cg* cg, double* hyp, int32_t* info) {
+  double xf[6], fun;
+  int32_t nit, cst;
+  int64_t nfev, njev, nobj;
+  oi_cg_result(cg, xf, &fun, &nit, &cst, &nfev, &njev, &nobj);
+  if (info) {
+    info[0] = nit;
+    info[1] = cst;
+    info[2] = (int32_t)nfev;
+    info[3] = (int32_t)nobj;
   }
+  for (int q = 0; q < 5; ++q) hyp[q] = std::exp(xf[q]);
+}
+
+// out[8] = (fs, sd, prior sd, the 5 fitted hypers): NB1 code cell 5's row
+void write_fit(const CellOut& r, const double* hyp, double* out, int32_t* status) {
+  *status = r.status;
+  out[0] = r.fs;
+  out[1] = r.sd;
+  out[2] = r.sprior;
+  for (int q = 0; q < 5; ++q) out[3 + q] = hyp[q];
 }
 
 }  // namespace
@@ -1115,9 +958,9 @@ extern "C" int oi_nystrom_batch(const double* xyt, const double* y, const int64_
   if (want_pred && !xs) return oi_set_last_error(OI_E_ARG, "pred needs xs");
   for (int64_t q = 0; q < ncell * 5; ++q)
     if (!(hyp[q] > 0.0)) return oi_set_last_error(OI_E_ARG, "hypers must be > 0");
-  oi_options o;
-  if (int rc = setup(opts, o)) return rc;
-  return guarded([&] {
+  const oi_options o = oi_resolve(opts);
+  if (int rc = oi_select_device(o)) return rc;
+  return oi_guarded([&] {
     BatchDev bd(b, want_pred ? xs : nullptr, o.device_inputs != 0, (hipStream_t)o.stream);
     Runner R(&bd.rows, b.nmax, b.mmax, ncell, o, want_obj, want_pred);
     std::vector<int64_t> cells(ncell);
@@ -1148,13 +991,12 @@ extern "C" int oi_nystrom_fit_batch(const double* xyt, const double* y, const in
   if (int rc = check_batch(b)) return rc;
   if (ncell == 0) return 0;
   if (!x0 || !xs || !out || !status) return oi_set_last_error(OI_E_ARG, "null pointer");
-  oi_options o;
-  if (int rc = setup(opts, o)) return rc;
+  const oi_options o = oi_resolve(opts);
+  if (int rc = oi_select_device(o)) return rc;
   // scipy: maxiter = len(x0) * 200 for the notebook's 5 hypers
   const int32_t maxiter = o.maxiter < 0 ? 1000 : o.maxiter;
-  return guarded([&] {
-    // one restated scipy CG per cell (6-slot; the sixth gradient is 0, which
-    // leaves scipy's iteration unchanged), every round one pass over the cells
+  return oi_guarded([&] {
+    // one restated scipy CG per cell, every round one pass over the cells
     // still iterating
     std::vector<oi_cg*> cg(ncell, nullptr);
     struct Free {
@@ -1164,20 +1006,11 @@ extern "C" int oi_nystrom_fit_batch(const double* xyt, const double* y, const in
           if (p) oi_cg_destroy(p);
       }
     } free_{cg};
-    double x6[6];
-    for (int q = 0; q < 5; ++q) x6[q] = x0[q];
-    x6[5] = 0.0;
     std::vector<double> req(ncell * 6);
     std::vector<char> live(ncell, 0);
-    for (int64_t c = 0; c < ncell; ++c) {
-      cg[c] = oi_cg_create(x6, o.gtol, maxiter);
-      if (!cg[c]) throw std::bad_alloc();
-      const int rc = oi_cg_step(cg[c], req.data() + c * 6);
-      if (rc < 0) throw HipErr{"oi_cg_step failed"};
-      live[c] = rc == 1;
-    }
+    for (int64_t c = 0; c < ncell; ++c) live[c] = cg_start(cg[c], x0, o.gtol, maxiter, req.data() + c * 6);
     // cells are independent: split them into G groups (OI_NYS_GROUPS, default 2),
-    // each with its own stream and lanes, so one group's latency-bound batched
+    // each with its own stream, so one group's latency-bound batched
     // eigh overlaps the other's panels / objective pass; each group is
     // collected and re-queued as soon as its round is done
     int G = 2;
@@ -1210,46 +1043,22 @@ extern "C" int oi_nystrom_fit_batch(const double* xyt, const double* y, const in
         RG[g]->collect(res.data());
         for (size_t k = 0; k < qcells[g].size(); ++k) {
           const int64_t c = qcells[g][k];
-          const double g6[6] = {res[k].grad[0], res[k].grad[1], res[k].grad[2], res[k].grad[3],
-                                res[k].grad[4], 0.0};
-          if (oi_cg_feed(cg[c], res[k].nlz, g6) != 0) throw HipErr{"oi_cg_feed failed"};
-          const int rc = oi_cg_step(cg[c], req.data() + c * 6);
-          if (rc < 0) throw HipErr{"oi_cg_step failed"};
-          live[c] = rc == 1;
+          live[c] = cg_advance(cg[c], res[k], req.data() + c * 6);
         }
         queue(g);
       }
     }
     RG.clear();
     Runner R(&bd.rows, b.nmax, b.mmax, ncell, o, false, true);
-    std::vector<int64_t> cells;
-    std::vector<double> hyp;
     // NB1 code cell 5: GPR(approx=True) at the fitted hypers
-    cells.clear();
-    hyp.clear();
-    std::vector<double> xf(ncell * 6);
+    std::vector<int64_t> cells(ncell);
+    std::vector<double> hyp(ncell * 5);
     for (int64_t c = 0; c < ncell; ++c) {
-      double fun;
-      int32_t nit, cst;
-      int64_t nfev, njev, nobj;
-      oi_cg_result(cg[c], xf.data() + c * 6, &fun, &nit, &cst, &nfev, &njev, &nobj);
-      if (info) {
-        info[c * 4 + 0] = nit;
-        info[c * 4 + 1] = cst;
-        info[c * 4 + 2] = (int32_t)nfev;
-        info[c * 4 + 3] = (int32_t)nobj;
-      }
-      cells.push_back(c);
-      for (int q = 0; q < 5; ++q) hyp.push_back(std::exp(xf[c * 6 + q]));
+      cells[c] = c;
+      cg_readout(cg[c], hyp.data() + c * 5, info ? info + c * 4 : nullptr);
     }
     R.run(cells, hyp.data(), mean, res.data(), false, true);
-    for (int64_t c = 0; c < ncell; ++c) {
-      status[c] = res[c].status;
-      out[c * 8 + 0] = res[c].fs;
-      out[c * 8 + 1] = res[c].sd;
-      out[c * 8 + 2] = res[c].sprior;
-      for (int q = 0; q < 5; ++q) out[c * 8 + 3 + q] = hyp[c * 5 + q];
-    }
+    for (int64_t c = 0; c < ncell; ++c) write_fit(res[c], hyp.data() + c * 5, out + c * 8, status + c);
     return 0;
   });
 }
@@ -1330,11 +1139,7 @@ struct oi_nystrom_session {
     g.R->collect(res.data());
     for (size_t k = 0; k < g.inflight.size(); ++k) {
       const int64_t c = g.inflight[k];
-      const double g6[6] = {res[k].grad[0], res[k].grad[1], res[k].grad[2], res[k].grad[3], res[k].grad[4], 0.0};
-      if (oi_cg_feed(cg[c], res[k].nlz, g6) != 0) throw HipErr{"oi_cg_feed failed"};
-      const int rc = oi_cg_step(cg[c], req.data() + c * 6);
-      if (rc < 0) throw HipErr{"oi_cg_step failed"};
-      if (rc == 0) finished(c);
+      if (!cg_advance(cg[c], res[k], req.data() + c * 6)) finished(c);
     }
     g.inflight.clear();
     std::vector<int64_t> keep;
@@ -1357,32 +1162,15 @@ struct oi_nystrom_session {
     std::vector<CellOut> res(cap);
     for (int64_t a = 0; a < t.count; a += cap) {
       const int64_t b = std::min(t.count, a + cap);
-      std::vector<int64_t> cells;
-      std::vector<double> hyp;
+      std::vector<int64_t> cells(b - a);
+      std::vector<double> hyp((b - a) * 5);
       for (int64_t k = a; k < b; ++k) {
-        const int64_t c = t.first + k;
-        double xf[6], fun;
-        int32_t nit, cst;
-        int64_t nfev, njev, nobj;
-        oi_cg_result(cg[c], xf, &fun, &nit, &cst, &nfev, &njev, &nobj);
-        if (t.info) {
-          t.info[k * 4 + 0] = nit;
-          t.info[k * 4 + 1] = cst;
-          t.info[k * 4 + 2] = (int32_t)nfev;
-          t.info[k * 4 + 3] = (int32_t)nobj;
-        }
-        cells.push_back(c);
-        for (int q = 0; q < 5; ++q) hyp.push_back(std::exp(xf[q]));
+        cells[k - a] = t.first + k;
+        cg_readout(cg[t.first + k], hyp.data() + (k - a) * 5, t.info ? t.info + k * 4 : nullptr);
       }
       R.run(cells, hyp.data(), t.mean, res.data(), false, true);
-      for (int64_t k = a; k < b; ++k) {
-        const CellOut& r = res[k - a];
-        t.status[k] = r.status;
-        t.out[k * 8 + 0] = r.fs;
-        t.out[k * 8 + 1] = r.sd;
-        t.out[k * 8 + 2] = r.sprior;
-        for (int q = 0; q < 5; ++q) t.out[k * 8 + 3 + q] = hyp[(k - a) * 5 + q];
-      }
+      for (int64_t k = a; k < b; ++k)
+        write_fit(res[k - a], hyp.data() + (k - a) * 5, t.out + k * 8, t.status + k);
     }
     for (int64_t k = 0; k < t.count; ++k) {
       oi_cg_destroy(cg[t.first + k]);
@@ -1396,18 +1184,10 @@ struct oi_nystrom_session {
     while ((int64_t)g.active.size() < cap && !queue.empty()) {
       const int64_t c = queue.front();
       queue.pop_front();
-      double x6[6];
-      for (int q = 0; q < 5; ++q) x6[q] = x0[c * 5 + q];
-      x6[5] = 0.0;
-      cg[c] = oi_cg_create(x6, gtol, maxiter);
-      if (!cg[c]) throw std::bad_alloc();
-      const int rc = oi_cg_step(cg[c], req.data() + c * 6);
-      if (rc < 0) throw HipErr{"oi_cg_step failed"};
-      if (rc == 0) {
+      if (cg_start(cg[c], x0.data() + c * 5, gtol, maxiter, req.data() + c * 6))
+        g.active.push_back(c);
+      else
         finished(c);
-        continue;
-      }
-      g.active.push_back(c);
     }
   }
 
@@ -1446,20 +1226,21 @@ struct oi_nystrom_session {
 };
 
 extern "C" oi_nystrom_session* oi_nystrom_session_create(const oi_options* opts) {
-  oi_options o;
-  if (setup(opts, o)) return nullptr;
-  auto* s = new oi_nystrom_session();
-  s->o = o;
-  if (hipStreamCreateWithFlags(&s->io, hipStreamNonBlocking) != hipSuccess) {
-    delete s;
-    oi_set_last_error(OI_E_HIP, "hipStreamCreate failed");
+  const oi_options o = oi_resolve(opts);
+  if (oi_select_device(o)) return nullptr;
+  std::unique_ptr<oi_nystrom_session> s;
+  if (oi_guarded([&] {
+        s = std::make_unique<oi_nystrom_session>();
+        s->o = o;
+        HC(hipStreamCreateWithFlags(&s->io, hipStreamNonBlocking));
+        return 0;
+      }))
     return nullptr;
-  }
   s->maxiter = o.maxiter < 0 ? 1000 : o.maxiter;  // scipy: len(x0) * 200 for NB1's 5 hypers
   s->gtol = o.gtol;
   if (const char* e = getenv("OI_NYS_GROUPS")) s->G = std::max(1, atoi(e));
   if (const char* e = getenv("OI_NYS_CAP")) s->cap = std::max(1, atoi(e));
-  return s;
+  return s.release();
 }
 
 extern "C" int64_t oi_nystrom_session_submit(oi_nystrom_session* s, const double* xyt, const double* y,
@@ -1471,7 +1252,7 @@ extern "C" int64_t oi_nystrom_session_submit(oi_nystrom_session* s, const double
   if (int rc = check_batch(b)) return rc;
   if (ncell > 0 && (!x0 || !xs || !out || !status)) return oi_set_last_error(OI_E_ARG, "null pointer");
   int64_t ticket = -1;
-  const int rc = guarded([&] {
+  const int rc = oi_guarded([&] {
     HC(hipSetDevice(s->o.device));
     auto t = std::make_unique<NysTicket>();
     t->first = (int64_t)s->tab.size();
@@ -1509,7 +1290,7 @@ extern "C" int64_t oi_nystrom_session_submit(oi_nystrom_session* s, const double
 extern "C" int oi_nystrom_session_wait(oi_nystrom_session* s, int64_t ticket) {
   if (!s) return oi_set_last_error(OI_E_ARG, "null session");
   if (ticket >= (int64_t)s->tickets.size()) return oi_set_last_error(OI_E_ARG, "unknown ticket");
-  return guarded([&] {
+  return oi_guarded([&] {
     HC(hipSetDevice(s->o.device));
     s->wait(ticket);
     return 0;

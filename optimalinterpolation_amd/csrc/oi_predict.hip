@@ -37,18 +37,14 @@
 #include <string>
 #include <vector>
 
-#include "../../include/oi.h"
+#include "oi_host.h"
 #include "oi_linalg.h"
+#include "oi_matern.h"
 
 #pragma clang fp contract(off)
 
-extern "C" int oi_set_last_error(int code, const char* msg);  // oi_engine.cpp
-extern "C" void oi_profile_add(const char* name, int64_t launches, double ms, double flops,
-                               double bytes);  // oi_engine.cpp
-
 namespace {
 
-constexpr double SQRT3 = 1.7320508075688772;   // np.sqrt(3.)
 constexpr double LOG2PI = 1.8378770664093453;  // np.log(2 * np.pi)
 
 // One cell of a chunk (device pointers; the row of the descriptor array that
@@ -80,14 +76,9 @@ __global__ void __launch_bounds__(256) k_pm_scale(const PCell* __restrict__ cs) 
   if (i >= c.n + c.nt) return;
   const double* src = i < c.n ? c.x + (size_t)i * 3 : c.xs + (size_t)(i - c.n) * 3;
   double* dst = i < c.n ? c.sc + (size_t)i * 3 : c.xsc + (size_t)(i - c.n) * 3;
-  dst[0] = (SQRT3 * src[0]) / c.l0;
-  dst[1] = (SQRT3 * src[1]) / c.l1;
-  dst[2] = (SQRT3 * src[2]) / c.l2;
-}
-
-__device__ inline double matern32(double sf2, double d0, double d1, double d2) {
-  const double Q = sqrt(d0 * d0 + d1 * d1 + d2 * d2);  // scipy pdist / cdist 'euclidean'
-  return sf2 * ((1.0 + Q) * exp(-Q));
+  dst[0] = matern_scale(src[0], c.l0);
+  dst[1] = matern_scale(src[1], c.l1);
+  dst[2] = matern_scale(src[2], c.l2);
 }
 
 // scaled rows of the tile's 64 rows (si) and 64 columns (sj) into LDS, zero beyond n
@@ -241,72 +232,10 @@ __global__ void __launch_bounds__(256) k_pm_reduce(const PCell* __restrict__ cs)
 
 // ------------------------------------------------------------------- host --
 
-struct HipErr {
-  std::string msg;
-};
-struct NoMem {
-  std::string msg;
-};
-
-#define HC(expr)                                                                           \
-  do {                                                                                     \
-    hipError_t e_ = (expr);                                                                \
-    if (e_ != hipSuccess) throw HipErr{std::string(#expr) + ": " + hipGetErrorString(e_)}; \
-  } while (0)
-#define KCHK() HC(hipGetLastError())
-
-inline unsigned blocks(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-inline int64_t up(int64_t v, int64_t q) { return (v + q - 1) / q * q; }
-
 // opts.profile: HIP events around each stage of each chunk, summed per stage
 // into oi_profile_json
 enum { S_GEN, S_CHOL, S_SOLVE, S_REDUCE, S_COV, S_COUNT };
 const char* kStage[S_COUNT] = {"pm_generate", "pm_cholesky", "pm_solve", "pm_reduce", "pm_cov"};
-struct Stages {
-  bool on = false;
-  hipStream_t st = nullptr;
-  std::vector<hipEvent_t> ev;
-  std::vector<int> kind;
-  std::vector<double> fl, by;
-  void begin(int k, double flops, double bytes) {
-    if (!on) return;
-    kind.push_back(k);
-    fl.push_back(flops);
-    by.push_back(bytes);
-    rec();
-  }
-  void end() {
-    if (on) rec();
-  }
-  void rec() {
-    hipEvent_t e;
-    HC(hipEventCreate(&e));
-    ev.push_back(e);
-    HC(hipEventRecord(e, st));
-  }
-  void flush() {  // after the stream has been synchronised
-    for (size_t q = 0; q < kind.size(); ++q) {
-      float t = 0.f;
-      HC(hipEventElapsedTime(&t, ev[2 * q], ev[2 * q + 1]));
-      oi_profile_add(kStage[kind[q]], 1, t, fl[q], by[q]);
-    }
-    for (auto e : ev) (void)hipEventDestroy(e);
-    ev.clear();
-    kind.clear();
-    fl.clear();
-    by.clear();
-  }
-  ~Stages() {
-    for (auto e : ev) (void)hipEventDestroy(e);
-  }
-};
-
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
 
 // Workspace of one cell in doubles.  Per-cell arrays are rounded to 32 doubles
 // (256 bytes); the chunk-wide arrays (inputs, targets, outputs, cov, flags)
@@ -361,15 +290,9 @@ extern "C" int oi_gpr_predict_multi(const double* xyt, const double* z, const in
     if (Np * Np >= LIM || (nt + 1) * n >= LIM || nt * nt >= LIM)
       return oi_set_last_error(OI_E_ARG, "cell too large (K, X or cov reaches 2 GiB)");
   }
-  oi_options o;
-  oi_options_default(&o);
-  if (opts) o = *opts;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return oi_set_last_error(OI_E_NODEV, "no HIP device available");
-  if (o.device < 0 || o.device >= ndev) return oi_set_last_error(OI_E_ARG, "bad device ordinal");
-  if (hipSetDevice(o.device) != hipSuccess) return oi_set_last_error(OI_E_HIP, "hipSetDevice failed");
-  try {
+  const oi_options o = oi_resolve(opts);
+  if (int rc = oi_select_device(o)) return rc;
+  return oi_guarded([&] {
     const bool host_in = o.device_inputs == 0, want_cov = cov != nullptr;
     hipStream_t st = (hipStream_t)o.stream;
     // chunks: consecutive cells while their workspace fits the budget
@@ -393,11 +316,10 @@ extern "C" int oi_gpr_predict_multi(const double* xyt, const double* z, const in
       biggest = std::max(biggest, cur);
     }
     cuts.push_back(ncell);
-    DevBuf ws;
-    HC(hipMalloc(&ws.p, (size_t)biggest * 8));
+    DevBuf ws((size_t)biggest * 8);
     oila::Stager la;
     la.bind(st);
-    Stages sg;
+    StageTimer sg(kStage, S_COUNT);
     sg.on = o.profile != 0;
     sg.st = st;
     std::vector<PCell> cells;
@@ -526,17 +448,9 @@ extern "C" int oi_gpr_predict_multi(const double* xyt, const double* z, const in
       covoff += cc;
       // the next chunk reuses the workspace and the descriptor ring
       HC(hipStreamSynchronize(st));
-      if (sg.on) sg.flush();
+      sg.flush();
       la.reset();
     }
     return 0;
-  } catch (const HipErr& e) {
-    return oi_set_last_error(OI_E_HIP, e.msg.c_str());
-  } catch (const oila::LinalgErr& e) {
-    return oi_set_last_error(OI_E_HIP, e.msg.c_str());
-  } catch (const NoMem& e) {
-    return oi_set_last_error(OI_E_NOMEM, e.msg.c_str());
-  } catch (const std::bad_alloc&) {
-    return oi_set_last_error(OI_E_NOMEM, "host allocation failed");
-  }
+  });
 }

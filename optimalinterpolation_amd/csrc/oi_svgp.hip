@@ -33,11 +33,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/oi.h"
-
-extern "C" int oi_set_last_error(int code, const char* msg);  // oi_engine.cpp
-extern "C" void oi_profile_add(const char* name, int64_t launches, double ms, double flops,
-                               double bytes);  // oi_engine.cpp
+#include "oi_host.h"
 
 namespace {
 
@@ -629,31 +625,6 @@ __global__ void __launch_bounds__(NT_MAX) k_svgp_train(
   if (tdbg && c == 0 && tid < 16) tdbg[tid] = s.tacc[tid];
 }
 
-struct HipErr {
-  std::string msg;
-};
-#define HC(expr)                                                                            \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess) throw HipErr{std::string(#expr) + ": " + hipGetErrorString(e_)}; \
-  } while (0)
-
-struct Buf {
-  void* p = nullptr;
-  explicit Buf(size_t bytes) {
-    if (bytes) HC(hipMalloc(&p, bytes));
-  }
-  ~Buf() {
-    if (p) (void)hipFree(p);
-  }
-  Buf(const Buf&) = delete;
-  Buf& operator=(const Buf&) = delete;
-  template <class T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
-
 double inv_softplus(double v) { return v + std::log(-std::expm1(-v)); }
 
 }  // namespace
@@ -680,16 +651,10 @@ extern "C" int oi_svgp_batch(const double* xyt, const double* y, const int64_t* 
       if (!(init[c * 6 + q] > (q == 4 ? 1e-6 : 0.0)))
         return oi_set_last_error(OI_E_ARG, "lengthscales / variances must be > 0 (noise > 1e-6)");
   }
-  oi_options o;
-  oi_options_default(&o);
-  if (opts) o = *opts;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return oi_set_last_error(OI_E_NODEV, "no HIP device available");
-  if (o.device < 0 || o.device >= ndev) return oi_set_last_error(OI_E_ARG, "bad device ordinal");
-  if (hipSetDevice(o.device) != hipSuccess) return oi_set_last_error(OI_E_HIP, "hipSetDevice failed");
+  const oi_options o = oi_resolve(opts);
+  if (int rc = oi_select_device(o)) return rc;
   hipStream_t st = (hipStream_t)o.stream;
-  try {
+  return oi_guarded([&] {
     const int P = oi_svgp_param_count(M);
     const int nlog = log_every > 0 ? (iterations + log_every - 1) / log_every : 0;
     const int64_t N = offs[ncell];
@@ -705,10 +670,10 @@ extern "C" int oi_svgp_batch(const double* xyt, const double* y, const int64_t* 
       for (int e = 0; e < 3 * M; ++e) t[6 + e] = Z0[c * 3 * M + e];
       for (int i = 0; i < M; ++i) t[6 + 4 * M + i * (i + 1) / 2 + i] = 1.0;
     }
-    Buf dth((size_t)ncell * P * 8), dmom((size_t)ncell * 2 * P * 8), dg((size_t)ncell * P * 8),
+    DevBuf dth((size_t)ncell * P * 8), dmom((size_t)ncell * 2 * P * 8), dg((size_t)ncell * P * 8),
         dsc((size_t)ncell * 3 * M * panel_ld(batch) * 8), dxs((size_t)ncell * 3 * 8), dpred((size_t)ncell * 2 * 8),
         delbo((size_t)ncell * (nlog ? nlog : 1) * 8), dst((size_t)ncell * 4), doffs((ncell + 1) * 8);
-    Buf hx(o.device_inputs ? 0 : N * 3 * 8), hy(o.device_inputs ? 0 : N * 8);
+    DevBuf hx(o.device_inputs ? 0 : N * 3 * 8), hy(o.device_inputs ? 0 : N * 8);
     const double* dx = xyt;
     const double* dy = y;
     if (!o.device_inputs) {
@@ -723,7 +688,7 @@ extern "C" int oi_svgp_batch(const double* xyt, const double* y, const int64_t* 
     HC(hipMemcpyAsync(doffs.p, offs, (ncell + 1) * 8, hipMemcpyHostToDevice, st));
     Shape sh{M, batch, P, nlog, panel_ld(batch)};
     const bool timing = getenv("OI_SVGP_TIMING") && atoi(getenv("OI_SVGP_TIMING")) != 0;
-    Buf dtd(timing ? 16 * 8 : 0);
+    DevBuf dtd(timing ? 16 * 8 : 0);
     if (timing) HC(hipMemsetAsync(dtd.p, 0, 16 * 8, st));
     // LDS layout mode (see carve): 1 when the panels fit, else 0; OI_SVGP_PANELS
     // overrides (0 / 1 / 2), falling back to 0 where the request cannot hold
@@ -782,9 +747,5 @@ extern "C" int oi_svgp_batch(const double* xyt, const double* y, const int64_t* 
       HC(hipMemcpyAsync(elbo, delbo.p, (size_t)ncell * nlog * 8, hipMemcpyDeviceToHost, st));
     HC(hipStreamSynchronize(st));
     return 0;
-  } catch (const HipErr& e) {
-    return oi_set_last_error(OI_E_HIP, e.msg.c_str());
-  } catch (const std::bad_alloc&) {
-    return oi_set_last_error(OI_E_NOMEM, "allocation failed");
-  }
+  });
 }

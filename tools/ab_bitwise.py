@@ -1,7 +1,17 @@
 """Bitwise A/B of two builds of liboi.so on the same inputs (a refactor that
-must not change a single bit): objective + gradient at fixed hypers on cells
-from n = 1 to 3000 (every tile-boundary class), predict at FIXED_HYPERS, and
-full opt=True fits of a few day cells.  Usage (GPU box):
+must not change a single bit).  One small case per entry family:
+  main engine   objective + gradient at fixed hypers on cells from n = 1 to
+                3000 (every tile-boundary class), predict at FIXED_HYPERS, and
+                full opt=True fits of a few day cells
+  Nystrom       objective + predict, the one-shot fit and a session (two
+                batches) on cells that cross the pad quantum 32 and the 64-tile
+                in n and M
+  prediction    gpr_predict_multi with the covariance, n and nt around the
+                64-tile, in one chunk and in several
+  SVGP          a short Adam run with logging
+  day helpers   smooth_fields, ball query + gather
+  profile       stage names and launch counts of the two staged paths
+Usage (GPU box):
     python tools/ab_bitwise.py run OUT.npz        # with OI_LIB set as wanted
     python tools/ab_bitwise.py cmp A.npz B.npz"""
 import os
@@ -13,8 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def run(out):
-    from optimalinterpolation_amd import _lib, synthetic
+def _engine(_lib, synthetic):
     sizes = [1, 2, 40, 63, 64, 65, 128, 129, 200, 257, 333, 700, 1100, 1600, 2300, 3000]
     cells = synthetic.make_cells(sizes, seed=77)
     h = np.tile(np.array([np.log(2e5), np.log(2.5e5), np.log(7.), np.log(4e-3), np.log(1e-3), 0.]), (len(sizes), 1))
@@ -24,15 +33,115 @@ def run(out):
     day = synthetic.make_day(seed=0, max_cells=40)
     fit, fst, info = _lib.gpr_batch(day.xyt, day.z, day.offs, day.xs, day.mean,
                                     x0=np.array([np.log(25e3), np.log(25e3), 0, 0, 0, np.log(.1)]), opt=True, info=True)
-    np.savez(out, nlz=nlz, grad=grad, st=st, pred=pred, pst=pst, fit=fit, fst=fst, info=info)
+    return dict(nlz=nlz, grad=grad, st=st, pred=pred, pst=pst, fit=fit, fst=fst, info=info)
+
+
+def _stages(_lib, prefix):
+    """Sorted stage names and launches of the stages called `prefix`* (no times)."""
+    k = _lib.profile_json()['kernels']
+    names = sorted(n for n in k if n.startswith(prefix))
+    return np.array(names), np.array([k[n]['launches'] for n in names], dtype=np.int64)
+
+
+def _nystrom(_lib, synthetic):
+    from optimalinterpolation_amd import nystrom
+    ns, Ms = [70, 130, 200, 260], np.array([20, 33, 64, 65])
+    c = synthetic.make_cells(ns, seed=5)
+    y = c.z - c.mean
+    sel, soffs = nystrom._ragged_sel(c.offs, Ms)
+    hyp = np.tile(synthetic.FIXED_HYPERS, (len(ns), 1))
+    args = (c.xyt, y, c.offs, sel, soffs, hyp)
+    nlz, grad, pred, st = _lib.nystrom_batch(*args, xs=c.xs, mean=c.mean)
+    _lib.profile_reset()
+    _lib.nystrom_batch(*args, xs=c.xs, mean=c.mean, profile=True)
+    names, launches = _stages(_lib, 'nys_')
+    x0 = nystrom.default_x0()
+    fit, fst, finfo = _lib.nystrom_fit_batch(c.xyt, y, c.offs, sel, soffs, x0, c.xs, c.mean, maxiter=100)
+    with _lib.NystromSession(maxiter=100) as s:
+        t = []
+        for a, b in [(0, 2), (2, 4)]:
+            po = c.offs[a:b + 1] - c.offs[a]
+            ps, pso = nystrom._ragged_sel(po, Ms[a:b])
+            t.append(s.submit(c.xyt[c.offs[a]:c.offs[b]], y[c.offs[a]:c.offs[b]], po, ps, pso, x0, c.xs[a:b], c.mean))
+        res = [s.wait(k) for k in t]
+    return dict(nys_nlz=nlz, nys_grad=grad, nys_pred=pred, nys_st=st, nys_stage_names=names,
+                nys_stage_launches=launches, nys_fit=fit, nys_fit_st=fst, nys_fit_info=finfo,
+                nys_ses=np.concatenate([r[0] for r in res]), nys_ses_st=np.concatenate([r[1] for r in res]),
+                nys_ses_info=np.concatenate([r[2] for r in res]))
+
+
+def _predict(_lib, synthetic):
+    ns, nts = [1, 63, 64, 65, 130], [1, 64, 65]
+    sizes = [n for n in ns for _ in nts]
+    c = synthetic.make_cells(sizes, seed=9)
+    rng = np.random.default_rng(10)
+    toffs = np.concatenate([[0], np.cumsum(nts * len(ns))])
+    xs = np.repeat(c.xs, nts * len(ns), axis=0) + rng.normal(0, 1.0, (toffs[-1], 3)) * [5e4, 5e4, 1.0]
+    hyp = np.tile(synthetic.FIXED_HYPERS, (len(sizes), 1))
+    args = (c.xyt, c.z, c.offs, xs, toffs, c.mean, hyp)
+    fs, sd, lz, cov, st = _lib.gpr_predict_multi(*args, cov=True)
+    # the largest cell needs ~63 000 doubles, all of them ~360 000: 1 MiB (131 072) makes >= 3 chunks
+    fs2, sd2, lz2, cov2, st2 = _lib.gpr_predict_multi(*args, cov=True, pool_bytes=1 << 20)
+    _lib.profile_reset()
+    _lib.gpr_predict_multi(*args, cov=True, pool_bytes=1 << 20, profile=True)
+    names, launches = _stages(_lib, 'pm_')
+    assert launches.max() >= 2, "pool_bytes did not force a second chunk"
+    return dict(pm_fs=fs, pm_sd=sd, pm_lz=lz, pm_cov=cov, pm_st=st, pm_fs2=fs2, pm_sd2=sd2, pm_lz2=lz2,
+                pm_cov2=cov2, pm_st2=st2, pm_stage_names=names, pm_stage_launches=launches)
+
+
+def _svgp(_lib):
+    rng = np.random.default_rng(11)
+    n, M, nc = 90, 8, 2
+    x = np.stack([rng.uniform(-3e5, 3e5, nc * n), rng.uniform(-3e5, 3e5, nc * n),
+                  rng.integers(0, 9, nc * n).astype(float)], 1)
+    y = 0.3 + 0.05 * np.sin(x[:, 0] / 1e5) + rng.normal(0, 0.02, nc * n)
+    Z = np.stack([x[k * n:k * n + M] for k in range(nc)])
+    init = np.tile([25e3, 25e3, 1.0, 1.0, 0.1, 0.3], (nc, 1))
+    xs = np.tile([1e4, -2e4, 4.0], (nc, 1))
+    pred, st, params, elbo = _lib.svgp_batch(x, y, [0, n, 2 * n], Z, init, xs, batch=16, iterations=50,
+                                             log_every=10, seed=3, want_params=True)
+    return dict(svgp_pred=pred, svgp_st=st, svgp_params=params, svgp_elbo=elbo)
+
+
+def _day(_lib):
+    rng = np.random.default_rng(12)
+    f = rng.normal(0.3, 0.1, (2, 40, 40))
+    f[rng.random(f.shape) < 0.3] = np.nan
+    mask = (rng.random((40, 40)) < 0.8).astype(float)
+    g = np.arange(-4, 5)
+    kern = np.exp(-(g[:, None] ** 2 + g[None, :] ** 2) / 2.0)
+    sm = _lib.smooth_fields(f, 1.0, mask, kern / kern.sum())
+    pts = rng.uniform(0, 1e6, (500, 2))
+    offs, idx = _lib.ball_query(pts, rng.uniform(0, 1e6, (20, 2)), 2e5)
+    cols = [pts[:, 0], pts[:, 1], rng.integers(0, 9, 500).astype(float), rng.normal(0, 1, 500)]
+    xyt, z = _lib.gather_rows(*cols, idx)
+    return dict(day_smooth=sm, day_offs=offs, day_idx=idx, day_xyt=xyt, day_z=z)
+
+
+def run(out):
+    from optimalinterpolation_amd import _lib, synthetic
+    r = _engine(_lib, synthetic)
+    r.update(_nystrom(_lib, synthetic))
+    r.update(_predict(_lib, synthetic))
+    r.update(_svgp(_lib))
+    r.update(_day(_lib))
+    np.savez(out, **r)
 
 
 def cmp(a, b):
     A, B = np.load(a), np.load(b)
-    bad = [k for k in A.files if not np.array_equal(A[k], B[k], equal_nan=True)]
+
+    def same(x, y):
+        return np.array_equal(x, y, equal_nan=x.dtype.kind == 'f')
+    bad = [k for k in A.files if k not in B.files or not same(A[k], B[k])]
     for k in bad:
-        d = np.abs(A[k].astype(float) - B[k].astype(float))
-        print(f"DIFF {k}: max abs {np.nanmax(d):.3e} at {np.unravel_index(np.nanargmax(d), d.shape)}")
+        if k in B.files and A[k].shape == B[k].shape and A[k].dtype.kind in 'fi' and A[k].size:
+            d = np.abs(A[k].astype(float) - B[k].astype(float))
+            print(f"DIFF {k}: max abs {np.nanmax(d):.3e} at {np.unravel_index(np.nanargmax(d), d.shape)}")
+        else:
+            print(f"DIFF {k}: {A[k] if A[k].size < 40 else A[k].shape} vs "
+                  f"{(B[k] if B[k].size < 40 else B[k].shape) if k in B.files else 'missing'}")
     print("bitwise equal" if not bad else f"{len(bad)} arrays differ", [f for f in A.files])
     return 0 if not bad else 1
 
