@@ -92,8 +92,9 @@ int oi_launch_diag_factor(const OiCell* cells, const int32_t* list, int ncell, i
 // the panels stream the L tiles and apply Dinv_jj to the finished sum (post-form);
 // fuse_diag: the look-ahead workgroup also factors diagonal tile j+1 (else
 // oi_launch_diag_factor(j+1) follows)
+// (chol_panel: j odd, finishes what the even panel of j - 1 left to pair k = j - 1)
 int oi_launch_chol_panel(const OiCell* cells, const int32_t* list, int ncell, int maxT, int j,
-                         int kbeg, int with_trtri, int fuse_diag, void* stream);
+                         int with_trtri, int fuse_diag, void* stream);
 int oi_launch_panel4(const OiCell* cells, const int32_t* list, int ncell, int maxT, int j, int with_trtri,
                      int fuse_diag, void* stream);
 int oi_launch_panel_even(const OiCell* cells, const int32_t* list, int ncell, int maxT, int j,

@@ -110,57 +110,39 @@ size_t cell_bytes(int64_t n, bool eval) {
 }
 
 // ------------------------------------------------------------- profiling
-enum KernelId { K_BUILD, K_CHOL, K_TRSM, K_EVEN, K_LAUUM, K_FINAL, K_EVEN4, K_COUNT };
-const char* kKernelName[K_COUNT] = {"k_build", "k_diag_factor", "k_chol_panel", "k_panel_even",
+enum KernelId { K_DIAG, K_CHOL_PANEL, K_EVEN, K_LAUUM, K_FINAL, K_EVEN4, K_COUNT };
+const char* kKernelName[K_COUNT] = {"k_diag_factor", "k_chol_panel", "k_panel_even",
                                     "k_lauum_grad", "k_finalize", "k_panel4"};
 
-// Panel scheme, read per call from OI_PANEL:
-//   2 (default): even/odd block-column pairs share one stream (k_panel_even +
-//                k_chol_panel(kbeg = j-1)): half the L / W traffic of the
-//                one-column scheme and k_scale only every other column;
-//                +2.5 % on the day workload;
-//   1          : one-column left-looking panels, every column streams its
-//                whole block row of L (and of W = L^-1).
-bool legacy_panels() {
-  const char* e = getenv("OI_PANEL");
-  return e && atoi(e) == 1;
+// An engine's environment knobs, read once when it is built.
+int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
 }
-// Even-column panel core, read per call from OI_PANEL4: 1 (default) => k_panel4
-// (two block rows per workgroup on the 128 x 128 gemm4 core; day 137.2 vs
-// 135.5 cells/s back to back on one box, profiles/r03/), 0 => k_panel_even
-// (64 x 128 gemm2 core).  Post-form only.
-bool panel4_enabled() {
-  const char* e = getenv("OI_PANEL4");
-  return !(e && atoi(e) == 0);
-}
-// k_panel4 from even column OI_PANEL4_MINJ on (k_panel_even below it: with few
-// streamed pairs per workgroup the paired-row epilogue costs more than the
-// shared operand stream saves)
-int panel4_minj() {
-  const char* e = getenv("OI_PANEL4_MINJ");
-  return e ? atoi(e) : 0;
-}
-// ... and only in rounds whose largest cell has at least OI_PANEL4_MINT (12)
-// block columns: on small cells (config 2, n = 500, T = 8: 271 k vs 284 k
-// cells/s; config 1) k_panel_even's one-tile workgroups finish sooner, on the
-// day (T up to 35) k_panel4 wins (138.1 vs 136.3 cells/s with it from j = 8 on)
-int panel4_mint() {
-  const char* e = getenv("OI_PANEL4_MINT");
-  return e ? atoi(e) : 12;
-}
-// ... and only when the launch has at least OI_PANEL4_MINWG (512: two
-// k_panel4 workgroups per CU) workgroups -- the day's tail rounds of a few
-// slow-converging cells run the one-row kernel, twice as many workgroups
-int panel4_minwg() {
-  const char* e = getenv("OI_PANEL4_MINWG");
-  return e ? atoi(e) : 512;
-}
-// rounds of at least OI_FUSE_DIAG_MIN cells factor diagonal tile j+1 inside
-// column j's panel launch (k_diag_factor4w then runs for column 0 only)
-int fuse_diag_min() {
-  const char* e = getenv("OI_FUSE_DIAG_MIN");
-  return e ? atoi(e) : 1;
-}
+struct Knobs {
+  // Even-column panel core: k_panel4 (two block rows per workgroup on the
+  // 128 x 128 gemm4 core; day 137.2 vs 135.5 cells/s back to back on one box,
+  // profiles/r03/) unless OI_PANEL4=0 => k_panel_even (64 x 128 gemm2 core) ...
+  bool panel4 = env_int("OI_PANEL4", 1) != 0;
+  // ... and only in rounds whose largest cell has at least OI_PANEL4_MINT
+  // block columns: on small cells (config 2, n = 500, T = 8: 271 k vs 284 k
+  // cells/s; config 1) k_panel_even's one-tile workgroups finish sooner, on the
+  // day (T up to 35) k_panel4 wins (138.1 vs 136.3 cells/s with it from j = 8 on)
+  int panel4_mint = env_int("OI_PANEL4_MINT", 12);
+  // ... and only when the launch has at least OI_PANEL4_MINWG (two k_panel4
+  // workgroups per CU) workgroups -- the day's tail rounds of a few
+  // slow-converging cells run the one-row kernel, twice as many workgroups
+  int panel4_minwg = env_int("OI_PANEL4_MINWG", 512);
+  // rounds of at least OI_FUSE_DIAG_MIN cells factor diagonal tile j+1 inside
+  // column j's panel launch (k_diag_factor4w then runs for column 0 only)
+  int fuse_diag_min = env_int("OI_FUSE_DIAG_MIN", 1);
+  // debug: NaN-fill a cell's workspace so any read-before-write shows
+  bool poison = env_int("OI_POISON", 0) == 1;
+  // streams the resident cells are split over (measured no gain on the day
+  // workload, round 1)
+  int groups = std::max(1, std::min(8, env_int("OI_GROUPS", 1)));
+};
+
 // Executed MFMA flops per cell and launch (profile mode), mirroring the
 // kernels' wave masks (oi_masks.h): a 16x16 accumulator block over one
 // 16-deep k-chunk is 8192 flops.  gemm2 (k_panel_even: 8 waves, wr 0..1,
@@ -176,7 +158,7 @@ inline int live(unsigned m) { return __builtin_popcount(~m & 0xFu); }
 // masks), in BLK units
 constexpr double POST_BLOCKS = 160.0 / 4.0;
 
-double panel_even(int T, int n, int j, bool eval, bool post) {
+double panel_even(int T, int n, int j, bool eval) {
   const int rT = n - OI_NB * (T - 1), nf = T - 1 - j;
   auto factor_wg = [&](int x) {
     const int i = j + 1 + x, mlim = i == T - 1 ? rT : OI_NB;
@@ -188,12 +170,9 @@ double panel_even(int T, int n, int j, bool eval, bool post) {
                          (x == 0 && wc >= 2 ? upper_blocks(32 * wr, 32 * (wc - 2)) : 0u);
       if (s == 0xFu) continue;
       b += 16.0 * j;  // pairs p < j: 4 chunks x 4 blocks each
-      if (!post)
-        for (int c = 0; c < 4; ++c)
-          if ((s | (wc >= 2 ? 0xFu : cols_above(c, 32 * wc))) != 0xFu) b += 4;
     }
     if (x == 0) b += 64;  // the fresh L_j+1,j L_j+1,j^T product of the look-ahead
-    if (post) b += POST_BLOCKS;  // (A_ij - acc) Dinv_jj^T
+    b += POST_BLOCKS;     // (A_ij - acc) Dinv_jj^T
     return b;
   };
   double blocks = 0;
@@ -202,7 +181,7 @@ double panel_even(int T, int n, int j, bool eval, bool post) {
   if (nf > 2) blocks += (nf - 2) * factor_wg(1);
   if (eval && j > 0) {
     const bool has_next = j + 1 < T;
-    if (post) blocks += j * POST_BLOCKS;  // -acc Dinv_jj^T, one per W tile
+    blocks += j * POST_BLOCKS;  // -acc Dinv_jj^T, one per W tile
     for (int w = 0; w < 8; ++w) {
       const int wr = (w >> 2) & 1, wc = w & 3;
       const int nlim = ((wc < 2 && j == T - 1) || (wc >= 2 && j + 1 == T - 1)) ? rT : OI_NB;
@@ -255,44 +234,34 @@ double panel4(int T, int n, int j, bool eval) {
   return blocks * BLK;
 }
 
-double chol_panel(int T, int n, int j, int kbeg, bool eval, bool post) {
+// k_chol_panel(j), j odd: every tile streams the one pair k = j-1.  (All counts
+// are small whole numbers, exact in a double whatever the order of the sums.)
+double chol_panel(int T, int n, int j, bool eval) {
   const int rT = n - OI_NB * (T - 1), nf = T - 1 - j;
   auto factor_wg = [&](int x) {
     const int i = j + 1 + x;
-    double b = 0;
+    double b = POST_BLOCKS;  // Dinv_jj (A_ij^T - acc)
     for (int w = 0; w < 4; ++w) {
       const int wr = w >> 1, wc = w & 1;
       const unsigned s = i == T - 1 ? pad_skip(32 * wr, 32 * wc, OI_NB, rT) : 0u;
-      b += 4.0 * (j - kbeg) * live(s);
-      if (!post)
-        for (int c = 0; c < 4; ++c) b += live(s | rows_above(c, 32 * wr));  // the Dinv_jj pair
+      b += 4.0 * live(s);
       if (x == 0) b += 4.0 * j * live(lower_blocks(32 * wr, 32 * wc));  // look-ahead syrk
     }
     if (x == 0) b += 64;  // its fresh L_ij L_ij^T product
-    if (post) b += POST_BLOCKS;  // Dinv_jj (A_ij^T - acc)
     return b;
   };
   double blocks = 0;
   if (nf > 0) blocks += factor_wg(0);
   if (nf > 1) blocks += factor_wg(nf - 1);
   if (nf > 2) blocks += (nf - 2) * factor_wg(1);
-  if (eval && j > 0) {
+  if (eval) {
+    blocks += j * POST_BLOCKS;  // Dinv_jj (Vneg - acc), every W tile
     for (int w = 0; w < 4; ++w) {
       const int wr = w >> 1, wc = w & 1;
       const unsigned s = j == T - 1 ? pad_skip(32 * wr, 32 * wc, rT, OI_NB) : 0u;
-      // pair k = jj (B = W_jj,jj) when the tile starts there, pair k = j (A = Dinv_jj)
-      double tri_first = 0, dinv_last = 0;
-      for (int c = 0; c < 4; ++c) {
-        tri_first += live(s | cols_below(c, 32 * wc));
-        dinv_last += live(s | rows_above(c, 32 * wr));
-      }
-      if (post) dinv_last = POST_BLOCKS / 4;  // Dinv_jj (Vneg - acc), every W tile (per wave: 4 waves)
-      for (int jj = 0; jj < j && jj < kbeg; ++jj)  // extra pair: k = kbeg .. j
-        blocks += 4.0 * (j - kbeg) * live(s) + dinv_last;
-      // kfirst = jj (jj >= kbeg): pairs k = jj .. j-1, the first against W_jj,jj
-      const int lo = kbeg < j ? kbeg : j;
-      for (int jj = lo; jj < j; ++jj)
-        blocks += 4.0 * (j - jj - 1) * live(s) + tri_first + (post ? dinv_last : 0.0);
+      double tri = 0;  // jj = j-1: the pair's B = W_jj,jj
+      for (int c = 0; c < 4; ++c) tri += live(s | cols_below(c, 32 * wc));
+      blocks += 4.0 * (j - 1) * live(s) + tri;  // jj < j-1: the pair in full
     }
   }
   return blocks * BLK;
@@ -533,9 +502,7 @@ struct Slot {
 class Engine {
  public:
   Engine(Context& ctx, const oi_options& o, int64_t cap_hint)
-      : ctx_(ctx), o_(o), legacy_(legacy_panels()), panel4_(panel4_enabled()),
-        panel4_minj_(panel4_minj()), panel4_mint_(panel4_mint()), panel4_minwg_(panel4_minwg()),
-        fuse_diag_min_(fuse_diag_min()) {
+      : ctx_(ctx), o_(o) {
     HC(hipSetDevice(ctx.device));
     st_ = o.stream ? (hipStream_t)o.stream : ctx.own_stream;
     ss_ = ctx.sub_stream;
@@ -545,16 +512,12 @@ class Engine {
       return true;
     }();
     (void)debug_set;
-    const char* ep = getenv("OI_POISON");
-    poison_ = ep && atoi(ep) == 1;
     cap_ = (int)std::max<int64_t>(1, std::min<int64_t>(cap_hint, o.max_pool > 0 ? o.max_pool : 2048));
     slots_ = std::vector<Slot>(cap_);
     // Resident cells are split into G groups with their own stream: while one
     // group's round runs, the host consumes the other group's results and its
     // kernels fill the GPU around the first group's latency-bound launches.
-    G_ = 1;  // OI_GROUPS=2..8: measured no gain on the day workload (round 1)
-    if (const char* eg = getenv("OI_GROUPS")) G_ = std::max(1, std::min(8, atoi(eg)));
-    if (cap_ < 2 * G_) G_ = 1;
+    G_ = cap_ < 2 * knobs_.groups ? 1 : knobs_.groups;  // (OI_GROUPS; default 1)
     capG_ = (cap_ + G_ - 1) / G_;
     // one block per group, mirrored on the host, so a round uploads its cell
     // records, lists and cleared status words in ONE copy (and the status comes
@@ -724,9 +687,9 @@ class Engine {
   // fills the chip, else k_panel_even (one block row: twice the workgroups);
   // the two are bitwise equal (round 5), so the choice never changes a result
   bool use_panel4(int j, int maxT, int cnt, bool trtri) const {
-    if (!(panel4_ && j >= panel4_minj_ && maxT >= panel4_mint_)) return false;
+    if (!(knobs_.panel4 && maxT >= knobs_.panel4_mint)) return false;
     const int64_t wg = (int64_t)cnt * (((maxT - j) >> 1) + (trtri ? j / 2 : 0));
-    return wg >= panel4_minwg_;
+    return wg >= knobs_.panel4_minwg;
   }
 
   // The stream later submissions' device inputs are ordered after (the rounds
@@ -810,7 +773,7 @@ class Engine {
       sl.cell = c;
       sl.off = off;
       sl.bytes = bytes;
-      if (poison_)  // debug: NaN-fill the cell's workspace so any read-before-write shows
+      if (knobs_.poison)  // debug: NaN-fill the cell's workspace so any read-before-write shows
         HC(hipMemsetAsync(ctx_.arena.ptr(off), 0xFF, bytes, gr.st));
       OiCell& cd = hcell(s);
       std::memset(&cd, 0, sizeof(cd));
@@ -921,7 +884,7 @@ class Engine {
     int rc = 0;
     cur_cells = na;
     prep_s_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - tl0).count();
-    // (no k_build since round 5: the factor kernels generate K + sn2 I where they read it)
+    // (the factor kernels generate K + sn2 I where they read it)
     for (int j = 0; j < maxT; ++j) {
       int cnt = 0;
       while (cnt < na && hc(all_slots[cnt]).T > j) ++cnt;
@@ -932,40 +895,35 @@ class Engine {
       // round holds fewer than OI_FUSE_DIAG_MIN cells (the lone cell of config
       // 1: there a launch of its own is cheaper than the long look-ahead
       // workgroup); bitwise the same either way
-      const bool fuse = na >= fuse_diag_min_;
+      const bool fuse = na >= knobs_.fuse_diag_min;
       if (j == 0 || !fuse) {
-        mark(K_CHOL, false);
+        mark(K_DIAG, false);
         rc |= oi_launch_diag_factor(dc, dl_all, cnt, j, gst);
-        mark(K_CHOL, true);
+        mark(K_DIAG, true);
       }
-      const bool even = !legacy_ && (j % 2 == 0);
-      const int kbeg = (legacy_ || even) ? 0 : j - 1;
       // the last column of a round with no fitting cell has neither factor
       // tiles below the diagonal nor a W row: its panel launch would be empty
-      const bool empty_panel = j == maxT - 1 && ne == 0;
-      if (empty_panel) {
-      } else if (even) {
-        const int ke = use_panel4(j, maxT, cnt, ne > 0) ? K_EVEN4 : K_EVEN;
-        mark(ke, false);
-        if (ke == K_EVEN4)
-          rc |= oi_launch_panel4(dc, dl_all, cnt, maxT, j, ne > 0 ? 1 : 0, fuse, gst);
-        else
-          rc |= oi_launch_panel_even(dc, dl_all, cnt, maxT, j, ne > 0 ? 1 : 0, fuse, gst);
-        mark(ke, true);
-      } else {
-        mark(K_TRSM, false);
-        rc |= oi_launch_chol_panel(dc, dl_all, cnt, maxT, j, kbeg, ne > 0 ? 1 : 0, fuse, gst);
-        mark(K_TRSM, true);
-      }
+      if (j == maxT - 1 && ne == 0) continue;
+      // even/odd block-column pairs share one stream of the L / W tiles: the
+      // even panel (one of two bitwise-equal kernels) does columns j and j+1
+      // up to k < j, k_chol_panel(j+1) adds the pair k = j
+      const int kk = j % 2 ? K_CHOL_PANEL : use_panel4(j, maxT, cnt, ne > 0) ? K_EVEN4 : K_EVEN;
+      const int trtri = ne > 0 ? 1 : 0;
+      mark(kk, false);
+      if (kk == K_EVEN4)
+        rc |= oi_launch_panel4(dc, dl_all, cnt, maxT, j, trtri, fuse, gst);
+      else if (kk == K_EVEN)
+        rc |= oi_launch_panel_even(dc, dl_all, cnt, maxT, j, trtri, fuse, gst);
+      else
+        rc |= oi_launch_chol_panel(dc, dl_all, cnt, maxT, j, trtri, fuse, gst);
+      mark(kk, true);
       if (o_.profile) {  // executed MFMA flops, mirroring the kernels' masks (acct::)
         for (int k = 0; k < cnt; ++k) {
           const OiCell& cd = hc(all_slots[k]);
           const bool ev = cd.mode == OI_MODE_EVAL;
-          if (empty_panel) continue;
-          const int kk = even ? (use_panel4(j, maxT, cnt, ne > 0) ? K_EVEN4 : K_EVEN) : K_TRSM;
           const double f = kk == K_EVEN4 ? acct::panel4(cd.T, cd.n, j, ev)
-                           : kk == K_EVEN ? acct::panel_even(cd.T, cd.n, j, ev, true)
-                                          : acct::chol_panel(cd.T, cd.n, j, kbeg, ev, true);
+                           : kk == K_EVEN ? acct::panel_even(cd.T, cd.n, j, ev)
+                                          : acct::chol_panel(cd.T, cd.n, j, ev);
           kfl_[kk] += f;
           std::lock_guard<std::mutex> pl(g_prof_mu);
           g_byj[{kk, j}].flops += f;
@@ -1143,8 +1101,7 @@ class Engine {
 
   Context& ctx_;
   oi_options o_;
-  bool legacy_ = false, poison_ = false, panel4_ = false;
-  int panel4_minj_ = 0, panel4_mint_ = 12, panel4_minwg_ = 512, fuse_diag_min_ = 1;
+  const Knobs knobs_;
   hipStream_t st_ = nullptr, ss_ = nullptr;
   hipEvent_t ready_ = nullptr;
   int cap_ = 1, G_ = 1, capG_ = 1;

@@ -13,9 +13,9 @@
 //                  L_ij = (A_ij - sum_{k<j} L_ik L_jk^T) Dinv_jj^T, A_i,j+1 -=
 //                  sum_{k<j} L_ik L_j+1,k^T, look-ahead of diagonal tile j+1;
 //                  rows j and j+1 of W = L^-1 from one stream of W_k,jj
-//   k_chol_panel(j, kbeg = j-1), j odd: finishes column j / W row j with two
-//                  products per tile, look-ahead of tile j+1       (both) 2 n^3/3
-//                  (kbeg = 0: the one-column scheme, OI_PANEL=1)
+//   k_chol_panel(j), j odd: finishes column j / W row j with the one pair k = j-1
+//                  the even panel left out (two products per tile), look-ahead
+//                  of tile j+1                                     (both) 2 n^3/3
 //   (forward substitution z = L^-1 r runs inside the factorisation: k_diag_factor4w
 //                  applies Dinv_jj to block j, the panels subtract L_ij z_j; and
 //                  alpha = W^T z = K^-1 r (GPR:127) is accumulated as each W tile
@@ -96,70 +96,6 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double* red) {
     }
 }
 
-// Compensated (Neumaier) accumulation and double-double pair addition for
-// the objective's reductions (round 6, -DOI_COMP_SUM=1; off by default): the
-// gradient traces Sum (K^-1 - alpha alpha^T) o G, the trace, z^T z and the
-// log-determinant sum keep their rounding error at O(eps) of the result.
-// Measured on the day: k_lauum_grad1 6 % slower (48.2 vs 51.4
-// TF/s), the day 137.5 vs 141.8 cells/s, while the GPU objective's distance to
-// the reference at x0 did not move (the ulps there are in the entries, not the
-// sums) and at the fitted hypers it was already inside the reference's own
-// order noise -- so the default keeps the plain fixed-order sums (bitwise the
-// round-5 kernels).  No contraction inside (the error terms must be exact).
-#ifndef OI_COMP_SUM
-#define OI_COMP_SUM 0
-#endif
-__device__ __forceinline__ void nsum(double& s, double& c, double x) {
-#pragma clang fp contract(off)
-#if OI_COMP_SUM
-  const double t = s + x;
-  c += fabs(s) >= fabs(x) ? (s - t) + x : (x - t) + s;
-  s = t;
-#else
-  s += x;
-#endif
-}
-__device__ __forceinline__ void pair_add(double& s, double& c, double s2, double c2) {
-#pragma clang fp contract(off)
-#if OI_COMP_SUM
-  const double t = s + s2;
-  const double bp = t - s;
-  const double e = (s - (t - bp)) + (s2 - bp);
-  s = t;
-  c = (c + c2) + e;
-#else
-  s += s2;
-  c += c2;
-#endif
-}
-
-// block_sum for compensated pairs (s[q], c[q]): the same fixed tree, each
-// step a double-double addition; the result (s + c rounded once) in v[q] of
-// thread 0
-template <int NV, int NWAVES>
-__device__ __forceinline__ void block_sum_c(double (&s)[NV], double (&c)[NV], double* red) {
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-#pragma unroll
-  for (int q = 0; q < NV; ++q)
-    for (int o = 32; o >= 1; o >>= 1) {
-      const double s2 = __shfl_down(s[q], o, 64), c2 = __shfl_down(c[q], o, 64);
-      pair_add(s[q], c[q], s2, c2);
-    }
-  __syncthreads();
-  if (lane == 0)
-    for (int q = 0; q < NV; ++q) {
-      red[(w * NV + q) * 2] = s[q];
-      red[(w * NV + q) * 2 + 1] = c[q];
-    }
-  __syncthreads();
-  if (t == 0)
-    for (int q = 0; q < NV; ++q) {
-      double ss = red[2 * q], cc = red[2 * q + 1];
-      for (int ww = 1; ww < NWAVES; ++ww) pair_add(ss, cc, red[(ww * NV + q) * 2], red[(ww * NV + q) * 2 + 1]);
-      s[q] = ss + cc;
-    }
-}
-
 __device__ __forceinline__ bool decode_tri(int x, int T, int& i, int& j) {
   if (x >= T * (T + 1) / 2) return false;
   int ii = (int)((sqrt(8.0 * x + 1.0) - 1.0) * 0.5);
@@ -201,14 +137,14 @@ __device__ __forceinline__ bool xcd_cell_slot_lead0(int gx, int ncell, int& cell
 
 // ------------------------------------------------ the covariance, generated
 // A = M = D Kd D + sn2 I for the sites (K + sn2 I of GPR:93-94 / GPR:126,
-// oi_device.h; identity on padding) is never stored (round 5: k_build, which
-// wrote it once per round only for the factor kernels to read it back, is
-// gone).  The kernel that first reads a pristine tile generates it from the
+// oi_device.h; identity on padding) is never stored (the kernel that wrote
+// it once per round, only for the factor kernels to read it back, went in
+// round 5).  The kernel that first reads a pristine tile generates it from the
 // coordinates instead: k_diag_factor4w(0) the first diagonal tile, the even
 // panels every tile of their column j (and the partial update of column j+1),
-// k_chol_panel its column when kbeg = 0 and every look-ahead diagonal tile.
+// k_chol_panel its column at j = 1 and every look-ahead diagonal tile.
 // SiteBlk: the 64 sites of one block -- scaled coordinates sqrt(3) x_d / ell_d
-// (exactly k_build's and k_lauum_grad1's) and the site weights d, 0 past n.
+// (exactly k_lauum_grad1's) and the site weights d, 0 past n.
 struct SiteBlk {
   double u[3][NB];
   double d[NB];
@@ -272,9 +208,6 @@ __device__ __forceinline__ void mfma16x16(d4& acc, const double* Am, int la, boo
   }
 }
 
-#ifndef OI_LAUUM_EPI
-#define OI_LAUUM_EPI 1
-#endif
 // stage timestamps for tools/diag_engine_probe (compiled in only there)
 #ifdef OI_DIAG_TIMING
 // sums of the stamps over every diagonal factor block 0 runs (slot 15: calls);
@@ -328,13 +261,10 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // upper triangle is scratch) on four waves, As <- L with zeros above the
 // diagonal.  Returns the smallest pivot in wave 0 (+inf in the other waves;
 // minNum passes a NaN pivot over, as the reference's cholesky does).
-// Broadcasts (OI_POTRF_LDSB, round 6): the element the next column's pivot
-// waits for comes by v_readlane; the rest of column q (rows c0+q+2 ..) goes
-// through `bc` in LDS -- one store, then uniform-address reads, against two
-// v_readlane per element -- the same doubles in the same update order.
-#ifndef OI_POTRF_LDSB
-#define OI_POTRF_LDSB 1
-#endif
+// Broadcasts (round 6): the element the next column's pivot waits for comes by
+// v_readlane; the rest of column q (rows c0+q+2 ..) goes through `bc` in LDS
+// -- one store, then uniform-address reads, against two v_readlane per element
+// -- the same doubles in the same update order.
 // Y (optional): the tile's global storage -- panel J-1's columns of L, final,
 // are stored by waves 1-3 while wave 0 factors panel J (the last panel's by
 // the caller), instead of all 64 columns after the factorisation
@@ -363,25 +293,20 @@ __device__ __forceinline__ double potrf4w(double* As, double* bc, double* Y = nu
         const double l = d * il;
         const double qd = R[q] * il;
         R[q] = r == cc ? l : qd;
-        if (OI_POTRF_LDSB) {
-          // column q-1's updates of rows c0+q+1 .. (their broadcasts were read
-          // during this column's pivot), before column q's own updates of them
-          if (q >= 1 && q - 1 < 14)
+        // column q-1's updates of rows c0+q+1 .. (their broadcasts were read
+        // during this column's pivot), before column q's own updates of them
+        if (q >= 1 && q - 1 < 14)
 #pragma unroll
-            for (int s2 = q + 1; s2 < 16; ++s2) R[s2] -= qprev * bq[s2];
-          if (q < 15) R[q + 1] -= qd * rdlane(R[q], c0 + q + 1);
-          if (q < 14) {
-            double* bb = bc + 64 * (q & 1);
-            bb[r] = R[q];
+          for (int s2 = q + 1; s2 < 16; ++s2) R[s2] -= qprev * bq[s2];
+        if (q < 15) R[q + 1] -= qd * rdlane(R[q], c0 + q + 1);
+        if (q < 14) {
+          double* bb = bc + 64 * (q & 1);
+          bb[r] = R[q];
 #pragma unroll
-            for (int s2 = q + 2; s2 < 16; ++s2) bq[s2] = bb[c0 + s2];
-          }
-          qprev = qd;
-          __builtin_amdgcn_sched_barrier(0);  // (later columns' broadcasts not hoisted: registers)
-        } else {
-#pragma unroll
-          for (int s2 = q + 1; s2 < 16; ++s2) R[s2] -= qd * rdlane(R[q], c0 + s2);
+          for (int s2 = q + 2; s2 < 16; ++s2) bq[s2] = bb[c0 + s2];
         }
+        qprev = qd;
+        __builtin_amdgcn_sched_barrier(0);  // (later columns' broadcasts not hoisted: registers)
       }
 #pragma unroll
       for (int q = 0; q < 16; ++q) As[r * DW_LD + c0 + q] = r >= c0 + q ? R[q] : 0.0;
@@ -797,16 +722,18 @@ __device__ __forceinline__ void acc_load_neg(Quad& acc, const double* base) {
       for (int r = 0; r < 4; ++r) acc.c[mb][nb][r] = -gld(base + acc1_row(mb, r) * NB + acc1_col(nb));
 }
 
-// --------------------------------------------------- k_chol_panel(j)
+// --------------------------------------------------- k_chol_panel(j), j odd
+// The even panel of column j-1 summed k < j-1 into column j and W row j; this
+// kernel streams the one remaining pair k = j-1 and finishes them.
 // One 256-thread workgroup per output tile; logical slots of a cell:
 //   x <  T-1-j : tile (i = j+1+x, j) of the factor; slot 0 (i = j+1) then
 //                applies the update of diagonal tile j+1 (look-ahead) for
 //                k_diag_factor4w(j+1);
 //   x >= T-1-j : (eval) tile (j, jj = x-(T-1-j)) of W = L^-1.
-// The GEMM loop streams the L tiles and the Dinv_jj product is applied once
-// to the finished sum (post_left; "post-form"):
-//   L_ij^T  = Dinv_jj (A_ij^T - sum_{k=kbeg}^{j-1} L_jk L_ik^T)
-//   W_j,jj  = Dinv_jj (Vneg - sum_{k=kfirst}^{j-1} L_jk W_k,jj)   (Vneg = 0 if kfirst = jj)
+// The Dinv_jj product is applied once to the finished sum (post_left;
+// "post-form"), A'_ij and Vneg being what the even panel stored:
+//   L_ij^T  = Dinv_jj (A'_ij^T - L_j,j-1 L_i,j-1^T)
+//   W_j,jj  = Dinv_jj (Vneg - L_j,j-1 W_j-1,jj)   (jj = j-1: no Vneg, W_jj,jj triangular)
 // out(m, n) = sum_q Dinv[m][q] S(q, n), S(m, n) = base[m*64 + n] - acc(m, n)
 // (base null: the generated pristine tile, gen(n, m); both null: S = -acc).  S is staged in LDS at row stride LDSA = 80 (B operand:
 // rows k, k+1 of a 32-lane ds_read_b64 in opposite bank halves); Dinv_jj (column-major,
@@ -879,11 +806,12 @@ __device__ __forceinline__ void post_left(const Quad& acc, double* lds, const do
   __syncthreads();
 }
 
-// GEN = (kbeg == 0): the column's A_ij are still pristine and generated here
-// (its own instantiation: the generating epilogue would cost the common
-// kbeg = j - 1 launches a wave per SIMD)
+// GEN = (j == 1): k_panel_even(0) / k_panel4(0) had nothing to subtract from
+// column 1, so its A_ij are still pristine and generated here (its own
+// instantiation: the generating epilogue would cost the j > 1 launches a wave
+// per SIMD)
 template <bool GEN, bool FUSE>
-__device__ __forceinline__ void chol_slot(const OiCell& c, int j, int kbeg, int x, double* lds) {
+__device__ __forceinline__ void chol_slot(const OiCell& c, int j, int x, double* lds) {
   constexpr bool fuse = FUSE;
   const int T = c.T;
   if (j >= T || *c.status != OI_OK) return;
@@ -904,12 +832,12 @@ __device__ __forceinline__ void chol_slot(const OiCell& c, int j, int kbeg, int 
     // so its load overlaps the operand stream instead of following it:
     // afterwards S = A' - sum = -acc (post_left with no base)
     if (!GEN) acc_load_neg(acc, Y);
-    gemm1_kmajor<true>(acc, lds, 4 * (j - kbeg), psk, [=, &c](int p, const double*& a, const double*& b) {
-      a = tileL(c, j, kbeg + p);
-      b = tileL(c, i, kbeg + p);
+    gemm1_kmajor<true>(acc, lds, 4, psk, [=, &c](int, const double*& a, const double*& b) {
+      a = tileL(c, j, j - 1);
+      b = tileL(c, i, j - 1);
     });
-    // kbeg = 0 (j = 1 of the paired scheme, every j of OI_PANEL=1): A_ij is still
-    // pristine -- generated from the sites (the GEMM's last barrier freed lds)
+    // j = 1: A_ij is still pristine -- generated from the sites (the GEMM's
+    // last barrier freed lds)
     if (GEN) {
       SiteBlk* sbl = (SiteBlk*)lds;
       stage_sites(c, i, &sbl[0], threadIdx.x, 256);
@@ -990,19 +918,19 @@ __device__ __forceinline__ void chol_slot(const OiCell& c, int j, int kbeg, int 
   }
   const int jj = x - ntrsm;
   if (c.mode != OI_MODE_EVAL || jj >= j) return;
-  // kbeg > jj: W_j,jj holds Vneg = -sum_{k=jj}^{kbeg-1} L_jk W_k,jj (k_panel_even /
-  // k_panel4), so W_j,jj = Dinv_jj (Vneg - sum_{k=kbeg}^{j-1} L_jk W_k,jj)
-  const int kfirst = jj > kbeg ? jj : kbeg, extra = kbeg > jj ? 1 : 0;
+  // jj < j-1: W_j,jj holds Vneg = -sum_{k=jj}^{j-2} L_jk W_k,jj (k_panel_even /
+  // k_panel4), so W_j,jj = Dinv_jj (Vneg - L_j,j-1 W_j-1,jj);
+  // jj = j-1: the sum is the one pair, whose B = W_jj,jj (B(k, n) = 0 for k < n)
+  const bool tri = jj == j - 1;
   const double apre = alpha_preload(c, jj, j);
   // m = row of W block row j: padding rows of the last block are skipped
   const unsigned psk = j == T - 1 ? pad_skip(32 * wr, 32 * wc, rT, NB) : 0u;
   double* Wt = tileW(c, j, jj);
-  if (extra) acc_load_neg(acc, Wt);  // Vneg into the accumulators (as A'_ij above)
-  // pair k = jj: B = W_jj,jj (B(k, n) = 0 for k < n)
-  auto cm = [=](int ch) { return !extra && ch < 4 ? cols_below(ch, 32 * wc) : 0u; };
-  gemm1_kmajor<true>(acc, lds, 4 * (j - kfirst), psk, [=, &c](int p, const double*& a, const double*& b) {
-    a = tileL(c, j, kfirst + p);
-    b = tileW(c, kfirst + p, jj);
+  if (!tri) acc_load_neg(acc, Wt);  // Vneg into the accumulators (as A'_ij above)
+  auto cm = [=](int ch) { return tri ? cols_below(ch, 32 * wc) : 0u; };
+  gemm1_kmajor<true>(acc, lds, 4, psk, [=, &c](int, const double*& a, const double*& b) {
+    a = tileL(c, j, j - 1);
+    b = tileW(c, j - 1, jj);
   }, cm);
   post_left(acc, lds, nullptr, nullptr, Dj, Wt);  // W_j,jj = Dinv_jj (Vneg - sum), stored and staged
   alpha_update<256>(c, lds, XLD, jj, apre, lds + NB * XLD);  // alpha_jj += W_j,jj^T z_j
@@ -1012,11 +940,11 @@ template <bool GEN, bool FUSE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void k_chol_panel(const OiCell* __restrict__ cells,
                                                    const int32_t* __restrict__ list, int j,
-                                                   int kbeg, int gx, int ncell) {
+                                                   int gx, int ncell) {
   __shared__ __attribute__((aligned(16))) double lds[GEMM1_LDS];
   int ci, x;
   if (!xcd_cell_slot_lead0(gx, ncell, ci, x)) return;
-  chol_slot<GEN, FUSE>(cells[list[ci]], j, kbeg, x, lds);
+  chol_slot<GEN, FUSE>(cells[list[ci]], j, x, lds);
 }
 
 // --------------------------------------------------- k_panel_even(j), j even
@@ -1027,13 +955,13 @@ void k_chol_panel(const OiCell* __restrict__ cells,
 //   x <  T-1-j : row i = j+1+x of the factor:
 //                  L_ij      = (A_ij - sum_{k<j} L_ik L_jk^T) Dinv_jj^T
 //                  A_i,j+1  -= sum_{k<j} L_ik L_j+1,k^T     (partial update of
-//                              column j+1; k_chol_panel(j+1, kbeg=j) adds k = j)
+//                              column j+1; k_chol_panel(j+1) adds k = j)
 //                i = j+1 (x = 0) instead completes A_j+1,j+1 (look-ahead):
 //                  A_j+1,j+1 -= sum_{k<j} L_j+1,k L_j+1,k^T + L_j+1,j L_j+1,j^T
 //   x >= T-1-j : (eval) jj = x-(T-1-j) < j, rows j and j+1 of W = L^-1:
 //                  W_j,jj^T  = -(sum_{k=jj}^{j-1} W_k,jj^T L_jk^T) Dinv_jj^T
 //                  W_j+1,jj  = Vneg := -sum_{k=jj}^{j-1} L_j+1,k W_k,jj  (finished
-//                              by k_chol_panel(j+1, kbeg=j))
+//                              by k_chol_panel(j+1))
 // Accumulators come out transposed with respect to the tile storage, so each
 // 64x64 half goes through LDS and is written back with coalesced 16 B rows.
 enum { EMIT_STORE = 0, EMIT_SUB = 1, EMIT_NEG = 2, EMIT_GENSUB = 3 };
@@ -1201,7 +1129,7 @@ void k_panel_even(const OiCell* __restrict__ cells,
     emit_copy(lds, tileL(c, i, j), EMIT_STORE);
     fwd_update<GEMM_THREADS>(c, lds, XLD, i, pre, lds + NB * XLD);
     if (x != 0) {
-      // partial update of A_i,j+1 (empty at j = 0: k_chol_panel(1, kbeg = 0) generates the tile)
+      // partial update of A_i,j+1 (empty at j = 0: k_chol_panel(1) generates the tile)
       if (j > 0) emit_half(acc, 1, lds, tileL(c, i, j + 1), EMIT_GENSUB, &Ai1);
       return;
     }
@@ -1608,17 +1536,13 @@ __device__ __forceinline__ void lauum_tile(const OiCell& c, int tile, double* ld
   }
   __syncthreads();
   const double sf2 = c.hyp[3];
-  double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, cs[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   for (int mb = 0; mb < 2; ++mb)
     for (int nb = 0; nb < 2; ++nb)
       for (int r = 0; r < 4; ++r) {
         const int m = acc1_row(mb, r), nn = acc1_col(nb);
         const int a = i * NB + m, b = j * NB + nn;
         if (a >= n || b >= n || (i == j && m < nn)) continue;
-#if OI_LAUUM_EPI == 0  // timing experiments only (tools): no epilogue
-        s[3] += acc.c[mb][nb][r];
-        continue;
-#endif
         const double wgt = (a == b) ? 1.0 : 2.0;
         const double w0 = acc.c[mb][nb][r] - al[m] * al[64 + nn];  // (M^-1 - aa^T)_st
         const double w = (dl[m] * dl[64 + nn]) * w0;                // (D M^-1 D - uu^T)_st
@@ -1626,35 +1550,18 @@ __device__ __forceinline__ void lauum_tile(const OiCell& c, int tile, double* ld
         const double d1 = uQ[1 * 128 + m] - uQ[1 * 128 + 64 + nn];
         const double d2 = uQ[2 * 128 + m] - uQ[2 * 128 + 64 + nn];
         const double Q = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-#if OI_LAUUM_EPI == 2  // timing experiments only (tools): no exp
-        const double e = 1.0 - Q;
-#else
         const double e = exp(-Q);
-#endif
         const double K = sf2 * ((1.0 + Q) * e);
         const double q0 = uq[0 * 128 + m] - uq[0 * 128 + 64 + nn];
         const double q1 = uq[1 * 128 + m] - uq[1 * 128 + 64 + nn];
         const double q2 = uq[2 * 128 + m] - uq[2 * 128 + 64 + nn];
-#if OI_COMP_SUM
-        nsum(s[0], cs[0], wgt * (w * (sf2 * ((q0 * q0) * e))));
-        nsum(s[1], cs[1], wgt * (w * (sf2 * ((q1 * q1) * e))));
-        nsum(s[2], cs[2], wgt * (w * (sf2 * ((q2 * q2) * e))));
-        nsum(s[3], cs[3], wgt * (w * (2.0 * K)));
-        if (a == b) nsum(s[4], cs[4], w0);
-#else
         s[0] += wgt * (w * (sf2 * ((q0 * q0) * e)));
         s[1] += wgt * (w * (sf2 * ((q1 * q1) * e)));
         s[2] += wgt * (w * (sf2 * ((q2 * q2) * e)));
         s[3] += wgt * (w * (2.0 * K));
         if (a == b) s[4] += w0;
-#endif
       }
-#if OI_COMP_SUM
-  block_sum_c<5, 4>(s, cs, red);
-#else
-  (void)cs;
   block_sum<5, 4>(s, red);
-#endif
   if (t == 0) {
     double* pp = c.part + OI_PART_GRAD(0) + 5 * (size_t)tile;
     for (int q = 0; q < 5; ++q) pp[q] = s[q];
@@ -1673,7 +1580,7 @@ __global__ __launch_bounds__(256) void k_lauum_grad1(const OiCell* __restrict__ 
 // ---------------------------------------------------------- k_finalize
 // nlZ = r.alpha/2 + sum log diag L + n log(2 pi)/2 (GPR:128); dnlZ (GPR:131-138)
 __device__ __forceinline__ void finalize_cell(const OiCell& c) {
-  __shared__ double red[(OI_COMP_SUM ? 2 : 1) * 4 * 7];  // block_sum_c: (s, c) pairs
+  __shared__ double red[4 * 7];
   const int t = threadIdx.x, T = c.T, ntile = T * (T + 1) / 2;
   // the round's status rides home in the result row (one D2H copy per round)
   if (t == 0) c.out[OI_OUT_STATUS] = (double)*c.status;
@@ -1713,16 +1620,6 @@ __device__ __forceinline__ void finalize_cell(const OiCell& c) {
     return;
   }
   double v[7] = {0, 0, 0, 0, 0, 0, 0};
-#if OI_COMP_SUM
-  double cv[7] = {0, 0, 0, 0, 0, 0, 0};
-  for (int x = t; x < nslot; x += 256)
-    for (int q = 0; q < 5; ++q) nsum(v[q], cv[q], c.part[OI_PART_GRAD(ntile) + 5 * x + q]);
-  for (int k = t; k < T; k += 256) {
-    nsum(v[5], cv[5], c.part[OI_PART_PRED(ntile, T) + 3 * k]);  // r^T alpha = z^T z, z = L^-1 r
-    nsum(v[6], cv[6], c.part[OI_PART_LOGDET(ntile, T) + k]);
-  }
-  block_sum_c<7, 4>(v, cv, red);
-#else
   for (int x = t; x < nslot; x += 256)
     for (int q = 0; q < 5; ++q) v[q] += c.part[OI_PART_GRAD(ntile) + 5 * x + q];
   for (int k = t; k < T; k += 256) {
@@ -1730,7 +1627,6 @@ __device__ __forceinline__ void finalize_cell(const OiCell& c) {
     v[6] += c.part[OI_PART_LOGDET(ntile, T) + k];
   }
   block_sum<7, 4>(v, red);
-#endif
   if (t == 0) {
     // site form (oi_device.h): r^T alpha = SSW/sn2 + v^T M^-1 v,
     // sum log diag L = log det M / 2 + (n - m)/2 log sn2, tr Q += (n - m)/sn2 - SSW/sn2^2
@@ -1929,19 +1825,14 @@ extern "C" int oi_launch_diag_factor(const OiCell* cells, const int32_t* list, i
 }
 
 extern "C" int oi_launch_chol_panel(const OiCell* cells, const int32_t* list, int ncell, int maxT,
-                                    int j, int kbeg, int with_trtri, int fuse_diag, void* stream) {
+                                    int j, int with_trtri, int fuse_diag, void* stream) {
+  if (j < 1) return -1;  // the kernel streams pair k = j - 1
   const int gx = (maxT - 1 - j) + (with_trtri ? j : 0);
   if (ncell <= 0 || gx <= 0) return 0;
   const dim3 g(grid1(gx, ncell));
-  if (kbeg == 0)
-    if (fuse_diag)
-      hipLaunchKernelGGL((k_chol_panel<true, true>), g, dim3(256), 0, S(stream), cells, list, j, kbeg, gx, ncell);
-    else
-      hipLaunchKernelGGL((k_chol_panel<true, false>), g, dim3(256), 0, S(stream), cells, list, j, kbeg, gx, ncell);
-  else if (fuse_diag)
-    hipLaunchKernelGGL((k_chol_panel<false, true>), g, dim3(256), 0, S(stream), cells, list, j, kbeg, gx, ncell);
-  else
-    hipLaunchKernelGGL((k_chol_panel<false, false>), g, dim3(256), 0, S(stream), cells, list, j, kbeg, gx, ncell);
+  auto k = j == 1 ? (fuse_diag ? k_chol_panel<true, true> : k_chol_panel<true, false>)
+                  : (fuse_diag ? k_chol_panel<false, true> : k_chol_panel<false, false>);
+  hipLaunchKernelGGL(k, g, dim3(256), 0, S(stream), cells, list, j, gx, ncell);
   return ret();
 }
 

@@ -159,11 +159,8 @@ def test_gpr3d_n0_edge():
     assert info[0, 1] == 0 and info[0, 3] == 1
 
 
-@pytest.mark.parametrize('scheme', ['1', '2'])
-def test_panel_schemes_agree(scheme, monkeypatch):
-    """Both Cholesky panel schemes (OI_PANEL=1 one column per launch, =2 paired
-    columns sharing one stream) meet the T1 tolerance on tile-boundary sizes."""
-    monkeypatch.setenv('OI_PANEL', scheme)
+def _check_tile_boundary_sizes():
+    """SMLII and the predict block meet the T1 tolerance on tile-boundary sizes."""
     sizes = [63, 64, 65, 129, 200, 257, 700]
     cells = synthetic.make_cells(sizes, seed=11)
     h = np.tile(np.array([np.log(2e5), np.log(2.5e5), np.log(7.), np.log(4e-3), np.log(1e-3), 0.]),
@@ -174,9 +171,9 @@ def test_panel_schemes_agree(scheme, monkeypatch):
         x, y, _ = cells.cell(c)
         f, g = O.neg_log_ml(h[c], x, y, np.full(len(y), cells.mean))
         f = float(np.asarray(f).item())
-        assert abs(nlz[c] - f) <= RTOL * max(1.0, abs(f)), (scheme, sizes[c])
+        assert abs(nlz[c] - f) <= RTOL * max(1.0, abs(f)), sizes[c]
         S = grad_scale(h[c], x, y, np.full(len(y), cells.mean))
-        assert np.all(np.abs(grad[c] - g) <= RTOL * (np.abs(g) + S)), (scheme, sizes[c])
+        assert np.all(np.abs(grad[c] - g) <= RTOL * (np.abs(g) + S)), sizes[c]
     hyp = np.tile(synthetic.FIXED_HYPERS, (len(sizes), 1))
     out, st2, _ = _lib.gpr_batch(cells.xyt, cells.z, cells.offs, cells.xs, cells.mean, opt=False, hyp=hyp)
     for c in range(len(sizes)):
@@ -184,6 +181,13 @@ def test_panel_schemes_agree(scheme, monkeypatch):
         fs, sd, lZ = O.predict(x, y, xs, cells.mean, hyp[c, :3], hyp[c, 3], hyp[c, 4])
         assert abs(out[c, 0] - fs[0]) <= RTOL * max(1, abs(fs[0]))
         assert abs(out[c, 1] - sd[0]) <= RTOL * max(1, abs(sd[0]))
+
+
+def test_panels_tile_boundary_sizes():
+    """The Cholesky panels as the engine picks them by default (paired columns
+    sharing one stream: an even-column kernel, then k_chol_panel for the odd
+    column) on sizes around the 64-tile."""
+    _check_tile_boundary_sizes()
 
 
 @pytest.mark.parametrize('knob,value', [('OI_PANEL4', '0'), ('OI_PANEL4_MINT', '0')])
@@ -196,7 +200,7 @@ def test_alternate_kernels_agree(knob, value, monkeypatch):
     single-wave diagonal factors, the P-form panels with k_scale, the 128x128
     K^-1 kernel and the folded pair step)"""
     monkeypatch.setenv(knob, value)
-    test_panel_schemes_agree('2', monkeypatch)
+    _check_tile_boundary_sizes()
 
 
 def test_config5_size_n5000():

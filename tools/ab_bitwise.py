@@ -10,7 +10,8 @@ must not change a single bit).  One small case per entry family:
                 64-tile, in one chunk and in several
   SVGP          a short Adam run with logging
   day helpers   smooth_fields, ball query + gather
-  profile       stage names and launch counts of the two staged paths
+  profile       stage names and launch counts of the two staged paths; the main
+                engine's kernels with their launch counts and counted flops
 Usage (GPU box):
     python tools/ab_bitwise.py run OUT.npz        # with OI_LIB set as wanted
     python tools/ab_bitwise.py cmp A.npz B.npz"""
@@ -30,10 +31,20 @@ def _engine(_lib, synthetic):
     nlz, grad, st = _lib.nlml_grad_batch(cells.xyt, cells.z, np.full(len(cells.z), cells.mean), cells.offs, h)
     hyp = np.tile(synthetic.FIXED_HYPERS, (len(sizes), 1))
     pred, pst, _ = _lib.gpr_batch(cells.xyt, cells.z, cells.offs, cells.xs, cells.mean, opt=False, hyp=hyp)
+    # the same two calls profiled: the engine's launch counts and its executed-flop
+    # accounting per kernel (entries never launched are left out)
+    _lib.profile_reset()
+    _lib.nlml_grad_batch(cells.xyt, cells.z, np.full(len(cells.z), cells.mean), cells.offs, h, profile=True)
+    _lib.gpr_batch(cells.xyt, cells.z, cells.offs, cells.xs, cells.mean, opt=False, hyp=hyp, profile=True)
+    k = _lib.profile_json()['kernels']
+    names = sorted(n for n in k if n.startswith('k_') and k[n]['launches'] > 0)
+    prof = dict(eng_kernel_names=np.array(names),
+                eng_kernel_launches=np.array([k[n]['launches'] for n in names], dtype=np.int64),
+                eng_kernel_flops=np.array([k[n]['flops'] for n in names], dtype=np.float64))
     day = synthetic.make_day(seed=0, max_cells=40)
     fit, fst, info = _lib.gpr_batch(day.xyt, day.z, day.offs, day.xs, day.mean,
                                     x0=np.array([np.log(25e3), np.log(25e3), 0, 0, 0, np.log(.1)]), opt=True, info=True)
-    return dict(nlz=nlz, grad=grad, st=st, pred=pred, pst=pst, fit=fit, fst=fst, info=info)
+    return dict(nlz=nlz, grad=grad, st=st, pred=pred, pst=pst, fit=fit, fst=fst, info=info, **prof)
 
 
 def _stages(_lib, prefix):
