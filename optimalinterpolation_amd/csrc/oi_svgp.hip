@@ -278,6 +278,10 @@ constexpr size_t LDS_MAX = 160 * 1024;
 // One minibatch: loss (always) and, if grad, the gradient into g[P].
 // th: parameters; X/Y: the cell's rows; rows: stream batch number.
 // Scratch (global, per cell): X1, X3 [M*B].  Returns the loss.
+// FEW: the workgroup has fewer than 4 waves (OI_SVGP_THREADS < 256).  A
+// compile-time flag: with the stride of the kernel-derivative loop read at run
+// time, the default 1024-thread launch measured 0.3 % slower.
+template <bool FEW>
 __device__ double step(const double* __restrict__ th, const double* __restrict__ X,
                        const double* __restrict__ Y, int64_t n, uint64_t seed, int64_t batchno,
                        const Shape& sh, Lds& s, double* __restrict__ X1, double* __restrict__ X2,
@@ -449,12 +453,15 @@ __device__ double step(const double* __restrict__ th, const double* __restrict__
   }
   __syncthreads();
   tmark(s, 9);
-  // kernel derivatives: 4 threads per inducing row m (quarter of b's and j's each)
+  // kernel derivatives: 4 parts per inducing row m (quarter of b's and j's each),
+  // one wave per part; with fewer than 4 waves (FEW) each wave takes every nw-th
+  // part, so every part is computed and its gzp slice written at any thread
+  // count.  Without FEW the loop is the single pass it always was.
   double acc[4] = {0.0, 0.0, 0.0, 0.0};  // g_var, g_ls[3] (before the -2/ls^3 factor)
   {
-    const int m = tid & 63, part4 = tid >> 6, nparts = 4;
-    double gz[3] = {0.0, 0.0, 0.0};
-    if (m < M && part4 < nparts) {
+    const int m = tid & 63, nw = (int)blockDim.x >> 6, nparts = 4;
+    for (int part4 = tid >> 6; part4 < nparts && m < M; part4 += FEW ? nw : nparts) {
+      double gz[3] = {0.0, 0.0, 0.0};
       const double* zm = s.Zs + m * 3;
       for (int b = part4; b < B; b += nparts) {
         double e;
@@ -480,10 +487,9 @@ __device__ double step(const double* __restrict__ th, const double* __restrict__
           gz[d] += 2.0 * W * diff;
         }
       }
+      for (int d = 0; d < 3; ++d) s.gzp[(part4 * M + m) * 3 + d] = gz[d];
     }
     // gZ[m][d] = sum of the 4 parts * 2 / ls^2, fixed order
-    if (m < M && part4 < nparts)
-      for (int d = 0; d < 3; ++d) s.gzp[(part4 * M + m) * 3 + d] = gz[d];
     __syncthreads();
     if (tid < M)
       for (int d = 0; d < 3; ++d) {
@@ -564,6 +570,7 @@ __device__ void predict(const double* __restrict__ th, const double* xs, const S
 }
 
 // One workgroup = one cell, the whole training run.
+template <bool FEW>
 __global__ void __launch_bounds__(NT_MAX) k_svgp_train(
     const double* __restrict__ xyt, const double* __restrict__ y, const int64_t* __restrict__ offs,
     Shape sh, int iters, int log_every, uint64_t seed, double lr, double* __restrict__ theta,
@@ -595,7 +602,7 @@ __global__ void __launch_bounds__(NT_MAX) k_svgp_train(
   double b1t = 1.0, b2t = 1.0;
   int64_t used = 0, nl = 0;
   for (int k = 0; k < iters; ++k) {
-    step(th, X, Y, n, cseed, used, sh, s, X1, X2, X3, g, true, &ok);
+    step<FEW>(th, X, Y, n, cseed, used, sh, s, X1, X2, X3, g, true, &ok);
     ++used;
     // TF2 Adam
     b1t *= b1;
@@ -612,7 +619,7 @@ __global__ void __launch_bounds__(NT_MAX) k_svgp_train(
     __syncthreads();
     tmark(s, 11);
     if (log_every > 0 && k % log_every == 0) {  // the notebook's -training_loss() on the next batch
-      const double l = step(th, X, Y, n, cseed, used, sh, s, X1, X2, X3, g, false, &ok);
+      const double l = step<FEW>(th, X, Y, n, cseed, used, sh, s, X1, X2, X3, g, false, &ok);
       ++used;
       if (tid == 0 && elbo) elbo[c * sh.nlog + nl] = -l;
       ++nl;
@@ -698,20 +705,20 @@ extern "C" int oi_svgp_batch(const double* xyt, const double* y, const int64_t* 
       panels = (want == 1 && panels == 1) ? 1 : ((want == 2 && M <= batch) ? 2 : 0);
     }
     const size_t lb = lds_bytes(M, batch, panels);
-    HC(hipFuncSetAttribute((const void*)k_svgp_train, hipFuncAttributeMaxDynamicSharedMemorySize,
-                           (int)lb));
     // threads per cell (OI_SVGP_THREADS: 64..1024, multiple of 64); 1024 measured
     // fastest (more waves to hide the latency of the per-step dependency chains)
     int nt = 1024;
     if (const char* e = getenv("OI_SVGP_THREADS")) nt = atoi(e);
     nt = std::max(64, std::min(NT_MAX, nt / 64 * 64));
+    auto* kern = nt < 256 ? k_svgp_train<true> : k_svgp_train<false>;
+    HC(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (o.profile) {
       HC(hipEventCreate(&ev0));
       HC(hipEventCreate(&ev1));
       HC(hipEventRecord(ev0, st));
     }
-    hipLaunchKernelGGL(k_svgp_train, dim3((unsigned)ncell), dim3(nt), lb, st, dx, dy,
+    hipLaunchKernelGGL(kern, dim3((unsigned)ncell), dim3(nt), lb, st, dx, dy,
                        doffs.as<int64_t>(), sh, iterations, log_every, seed, lr, dth.as<double>(),
                        dmom.as<double>(), dg.as<double>(), dsc.as<double>(), dxs.as<double>(),
                        dpred.as<double>(), nlog ? delbo.as<double>() : nullptr, dst.as<int32_t>(),

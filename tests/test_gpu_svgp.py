@@ -9,6 +9,17 @@ deterministic minibatch stream.  Parity vs GPflow itself is unpinned
   parameters   |gpu - ref| <= TOL * max(1, |ref|)   (observed <= 5e-12 at 200
                steps, 1e-13 at the notebook's n = 4600, M = 50, B = 100)
   ELBO log     relative 1e-12;  predict_f mean / variance  1e-10
+
+Covered here: the default configuration (1024 threads, host-chosen layout) on
+trajectories of 15-1000 steps at M in {1, 8, 12, 16, 20, 50}, a three-cell batch
+against its single-cell calls, and the notebook-shaped Python surface.
+Covered in tests/test_gpu_svgp_config.py, at 12-20 steps and the same
+tolerance form: OI_SVGP_THREADS from 64 to 1024 and its rounding;
+OI_SVGP_PANELS unset / 0 / 1 / 2 with the mode each resolves to; M = 64,
+B = 256, M = B, M > B, B = 1, n = 1, a batch spanning several epochs;
+iterations = 0, log_every = 0, log_every not dividing or exceeding iterations;
+per-cell init rows and targets; status 1 for a cell with non-finite input and
+its batch-mates untouched; OI_SVGP_TIMING=1 leaving results unchanged.
 """
 import os
 

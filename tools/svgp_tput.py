@@ -1,6 +1,6 @@
 """SVGP kernel: time per step vs threads per cell and number of cells (diagnostic)."""
 import os, sys, time
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from oracle import svgp_oracle as O
 from optimalinterpolation_amd import _lib
@@ -23,5 +23,5 @@ for k in (1, 256, len(offs) - 1):
     t = time.time()
     pred, st, _, _ = _lib.svgp_batch(X[:k * n], Y[:k * n], offs[:k + 1], Z[:k], init, xs, batch=B, iterations=iters)
     dt = time.time() - t
-    print(f"threads {os.environ.get('OI_SVGP_THREADS', '256')} cells {k} iters {iters}: {dt:.3f} s, "
+    print(f"threads {os.environ.get('OI_SVGP_THREADS', '1024')} cells {k} iters {iters}: {dt:.3f} s, "
           f"{dt / iters * 1e6:.1f} us/step, {k * iters / dt:.0f} cell-steps/s, status {st.sum()}", flush=True)
