@@ -265,6 +265,45 @@ int oi_svgp_batch(const double* xyt, const double* y, const int64_t* offs, int64
                   const double* xs, double* pred, double* params, double* elbo, int32_t* status,
                   const oi_options* opts);
 
+/* A trained model put to use: GPflow's SVGP.predict_f / predict_y at any number
+ * of targets per cell, from the `params` rows oi_svgp_batch returned (or any
+ * rows of that layout).  Nothing is trained.
+ *   params [ncell x oi_svgp_param_count(M)] host; 1 <= M <= 64
+ *   xs     [T x 3]  targets of all cells, cell c owning rows
+ *                   toffs[c] .. toffs[c+1]-1 (a device pointer with
+ *                   opts->device_inputs); no target (nt = 0) is valid
+ *   toffs  [ncell+1] target offsets, toffs[0] = 0, non-decreasing
+ *   with_noise  0: predict_f;  1: predict_y of the Gaussian likelihood, i.e.
+ *                   softplus(lik_raw) + 1e-6 added to var (cov must be NULL:
+ *                   GPflow has no full-covariance predict_y)
+ *   mean   [T]      c + A'q_mu,  A = L^-1 K_us,  L = chol(K_uu + 1e-6 I)
+ *   var    [T]      kvar - sum A^2 + sum (q_sqrt' A)^2   (full_cov=False)
+ *   cov    or NULL: K_ss - A'A + (S'A)'(S'A) in full, cell c's nt x nt matrix
+ *                   row-major at offset sum_{k<c} nt_k^2; symmetric bit for
+ *                   bit, its diagonal bit for bit `var` (the diagonal of K_ss
+ *                   is kvar exactly); nt^2 doubles must stay below 2 GiB
+ *   status [ncell]  0 ok, 1 the K_uu Cholesky met a pivot that is not positive
+ *                   (non-finite parameters included): that cell's mean, var
+ *                   and cov are NaN, the other cells are untouched
+ * Cells are worked in chunks that fit opts->pool_bytes (0 => 60% of the free
+ * HBM); a cell that does not fit alone is OI_E_NOMEM.  A result depends on the
+ * cell and the target alone: not on the other cells or targets of the call,
+ * the chunking, or host / device inputs. */
+int oi_svgp_predict(const double* params, int32_t M, int64_t ncell, const double* xs,
+                    const int64_t* toffs, int32_t with_noise, double* mean, double* var,
+                    double* cov, int32_t* status, const oi_options* opts);
+
+/* GPflow's model.elbo((X, Y)) on ALL of each cell's data at the given params:
+ *   elbo[c] = sum_i [-log(2 pi)/2 - log(s2)/2 - ((y_i - mean_i)^2 + var_i)/(2 s2)]
+ *             - (q_mu.q_mu + sum S^2 - M - sum log S_ii^2) / 2
+ * -- the number two trained models are compared by (oi_svgp_batch's `elbo` log
+ * holds minibatch estimates of it).
+ *   xyt, y, offs as in oi_svgp_batch (device pointers with opts->device_inputs);
+ *   every cell needs n >= 1.  status as above; a failed cell's elbo is NaN. */
+int oi_svgp_elbo(const double* params, int32_t M, const double* xyt, const double* y,
+                 const int64_t* offs, int64_t ncell, double* elbo, int32_t* status,
+                 const oi_options* opts);
+
 /* ---- host optimiser (scipy 1.15 CG restated; see csrc/cg.hpp) ---- */
 typedef struct oi_cg oi_cg;
 /* x0: 6 log-hypers. gtol/maxiter as in oi_options (maxiter < 0 => 1200). */

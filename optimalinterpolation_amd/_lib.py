@@ -38,7 +38,8 @@ EXPORTS = ('oi_options_default', 'oi_gpr_batch', 'oi_nlml_grad_batch', 'oi_cg_cr
            'oi_nystrom_fit_batch', 'oi_svgp_batch', 'oi_svgp_param_count', 'oi_session_create',
            'oi_session_submit', 'oi_session_set_stream', 'oi_session_wait', 'oi_session_done',
            'oi_session_destroy', 'oi_nystrom_session_create', 'oi_nystrom_session_submit',
-           'oi_nystrom_session_wait', 'oi_nystrom_session_destroy', 'oi_gpr_predict_multi')
+           'oi_nystrom_session_wait', 'oi_nystrom_session_destroy', 'oi_gpr_predict_multi',
+           'oi_svgp_predict', 'oi_svgp_elbo')
 
 
 class OiOptions(ctypes.Structure):
@@ -125,6 +126,14 @@ def load():
                                       c_double_p, c_double_p, c_double_p, c_int32_p,
                                       ctypes.POINTER(OiOptions)]
         lib.oi_svgp_batch.restype = ctypes.c_int
+        lib.oi_svgp_predict.argtypes = [c_double_p, ctypes.c_int32, ctypes.c_int64, c_double_p,
+                                        c_int64_p, ctypes.c_int32, c_double_p, c_double_p,
+                                        c_double_p, c_int32_p, ctypes.POINTER(OiOptions)]
+        lib.oi_svgp_predict.restype = ctypes.c_int
+        lib.oi_svgp_elbo.argtypes = [c_double_p, ctypes.c_int32, c_double_p, c_double_p, c_int64_p,
+                                     ctypes.c_int64, c_double_p, c_int32_p,
+                                     ctypes.POINTER(OiOptions)]
+        lib.oi_svgp_elbo.restype = ctypes.c_int
         lib.oi_nystrom_session_create.argtypes = [ctypes.POINTER(OiOptions)]
         lib.oi_nystrom_session_create.restype = ctypes.c_void_p
         lib.oi_nystrom_session_submit.argtypes = [ctypes.c_void_p, c_double_p, c_double_p, c_int64_p,
@@ -653,6 +662,87 @@ def svgp_batch(xyt, y, offs, Z0, init, xs, batch=100, iterations=10000, log_ever
                            _ptr(status, ctypes.c_int32), ctypes.byref(o))
     _check(rc)
     return pred, status, params, elbo
+
+
+def _svgp_rows(params):
+    """``params`` as [ncell x P] rows and the M that P = 6 + 4 M + M (M + 1) / 2 belongs to."""
+    params = np.ascontiguousarray(params, dtype=np.float64)
+    if params.ndim == 1:
+        params = params[None]
+    if params.ndim != 2:
+        raise ValueError("params must be [ncell x P]")
+    for M in range(1, 65):
+        if 6 + 4 * M + M * (M + 1) // 2 == params.shape[1]:
+            return params, M
+    raise ValueError(f"params rows of length {params.shape[1]} belong to no M in [1, 64]")
+
+
+def svgp_predict(params, xs, toffs, with_noise=False, cov=False, **opt_kw):
+    """oi_svgp_predict: GPflow SVGP.predict_f (``with_noise``: predict_y) of
+    trained cells -- ``params`` [ncell x P] as svgp_batch(want_params=True)
+    returns them -- at ``xs`` [T x 3], cell c owning rows toffs[c]:toffs[c+1].
+    Returns (mean [T], var [T], cov | None, status [ncell]); ``cov`` is the flat
+    array of the cells' nt x nt matrices back to back (``split_cov``).  With
+    device_inputs=True ``xs`` is a torch device tensor."""
+    lib = load()
+    params, M = _svgp_rows(params)
+    ncell = params.shape[0]
+    toffs = np.ascontiguousarray(toffs, dtype=np.int64).reshape(-1)
+    if len(toffs) != ncell + 1 or toffs[0] != 0 or np.any(np.diff(toffs) < 0):
+        raise ValueError("inconsistent ragged batch")
+    T = int(toffs[-1])
+    if opt_kw.get('device_inputs'):
+        if xs.numel() != 3 * T:
+            raise ValueError("inconsistent ragged batch")
+        pxs = _dptr(xs)
+        _sync_producers(opt_kw.get('device', 0))
+    else:
+        xs = np.ascontiguousarray(xs, dtype=np.float64).reshape(-1, 3)
+        if xs.shape[0] != T:
+            raise ValueError("inconsistent ragged batch")
+        pxs = _ptr(xs, ctypes.c_double)
+    mean = np.empty(T)
+    var = np.empty(T)
+    nt = np.diff(toffs)
+    cova = np.empty(int((nt * nt).sum())) if cov else None
+    status = np.zeros(ncell, dtype=np.int32)
+    o = options(**opt_kw)
+    _check(lib.oi_svgp_predict(_ptr(params, ctypes.c_double), M, ncell, pxs,
+                               _ptr(toffs, ctypes.c_int64), 1 if with_noise else 0,
+                               _ptr(mean, ctypes.c_double), _ptr(var, ctypes.c_double),
+                               _ptr(cova, ctypes.c_double), _ptr(status, ctypes.c_int32),
+                               ctypes.byref(o)))
+    return mean, var, cova, status
+
+
+def svgp_elbo(params, xyt, y, offs, **opt_kw):
+    """oi_svgp_elbo: model.elbo((X, Y)) on all of each cell's data at ``params``
+    [ncell x P].  Returns (elbo [ncell], status [ncell]).  With
+    device_inputs=True ``xyt`` and ``y`` are torch device tensors."""
+    lib = load()
+    params, M = _svgp_rows(params)
+    ncell = params.shape[0]
+    offs = np.ascontiguousarray(offs, dtype=np.int64).reshape(-1)
+    if len(offs) != ncell + 1 or offs[0] != 0:
+        raise ValueError("inconsistent ragged batch")
+    if opt_kw.get('device_inputs'):
+        if xyt.numel() != 3 * offs[-1] or y.numel() != offs[-1]:
+            raise ValueError("inconsistent ragged batch")
+        px, py = _dptr(xyt), _dptr(y)
+        _sync_producers(opt_kw.get('device', 0))
+    else:
+        xyt = np.ascontiguousarray(xyt, dtype=np.float64).reshape(-1, 3)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        if offs[-1] != len(y) or xyt.shape[0] != len(y):
+            raise ValueError("inconsistent ragged batch")
+        px, py = _ptr(xyt, ctypes.c_double), _ptr(y, ctypes.c_double)
+    elbo = np.empty(ncell)
+    status = np.zeros(ncell, dtype=np.int32)
+    o = options(**opt_kw)
+    _check(lib.oi_svgp_elbo(_ptr(params, ctypes.c_double), M, px, py, _ptr(offs, ctypes.c_int64),
+                            ncell, _ptr(elbo, ctypes.c_double), _ptr(status, ctypes.c_int32),
+                            ctypes.byref(o)))
+    return elbo, status
 
 
 class CG:

@@ -10,7 +10,10 @@ cell runs on the GPU in one liboi call (``oi_svgp_batch``: one workgroup per
 cell, all iterations in one launch).  Differences from the notebook, by
 necessity: the minibatch stream is a deterministic keyed permutation (TF's
 shuffle RNG cannot be reproduced), and instead of a GPflow model object the
-final parameters come back as a dict.
+final parameters come back as a dict.  That dict is the trained model:
+``predict_f`` / ``predict_y`` / ``elbo`` below take it as GPflow's methods of
+the same names take ``self`` (``oi_svgp_predict`` / ``oi_svgp_elbo``; nothing
+is trained again).
 """
 import numpy as np
 
@@ -32,7 +35,41 @@ def unpack(theta, M):
     S[np.tril_indices(M)] = theta[6 + 4 * M:]
     return dict(lengthscales=sp(theta[:3]), kernel_variance=float(sp(theta[3])),
                 noise_variance=float(sp(theta[4])) + 1e-6, mean=float(theta[5]),
-                Z=theta[6:6 + 3 * M].reshape(M, 3), q_mu=theta[6 + 3 * M:6 + 4 * M], q_sqrt=S)
+                Z=theta[6:6 + 3 * M].reshape(M, 3), q_mu=theta[6 + 3 * M:6 + 4 * M], q_sqrt=S,
+                theta=theta)
+
+
+def _theta(model):
+    """The flat unconstrained row of a model dict (or the row itself)."""
+    return np.asarray(model['theta'] if isinstance(model, dict) else model, dtype=np.float64)
+
+
+def predict_f(model, Xnew, full_cov=False):
+    """GPflow ``model.predict_f(Xnew, full_cov)`` for a model returned by SVGP /
+    SVGP_batch: (mean [ns, 1], var [ns, 1]), or with ``full_cov`` the [ns, ns]
+    posterior covariance in place of the variance.  One GPU call
+    (``oi_svgp_predict``); nothing is trained."""
+    Xnew = np.asarray(Xnew, dtype=np.float64).reshape(-1, 3)
+    ns = len(Xnew)
+    m, v, cov, _ = _lib.svgp_predict(_theta(model), Xnew, [0, ns], cov=full_cov, **options)
+    return m.reshape(ns, 1), (cov.reshape(ns, ns) if full_cov else v.reshape(ns, 1))
+
+
+def predict_y(model, Xnew):
+    """GPflow ``model.predict_y(Xnew)`` (Gaussian likelihood): predict_f with the
+    noise variance added to the variance."""
+    Xnew = np.asarray(Xnew, dtype=np.float64).reshape(-1, 3)
+    ns = len(Xnew)
+    m, v, _, _ = _lib.svgp_predict(_theta(model), Xnew, [0, ns], with_noise=True, **options)
+    return m.reshape(ns, 1), v.reshape(ns, 1)
+
+
+def elbo(model, x, y):
+    """GPflow ``model.elbo((x, y))`` on all the data given (``oi_svgp_elbo``)."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1, 3)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    e, _ = _lib.svgp_elbo(_theta(model), x, y, [0, len(y)], **options)
+    return float(e[0])
 
 
 def SVGP_batch(xyt, y, offs, xs, Z, lengthscales, kernel_variance, noise_variance, mean,
@@ -60,10 +97,18 @@ def SVGP_batch(xyt, y, offs, xs, Z, lengthscales, kernel_variance, noise_varianc
 
 def SVGP(x, y, xs, Z, lengthscales=1, kernel_variance=1, noise_variance=None, mean=0,
          batchsize=None, iterations=10000, seed=0):
-    """NB2 SVGP for one cell: (mean [1,1], var [1,1], params dict).  As in the
-    notebook, noise_variance None means 0.1 * var(y) and batchsize None means n."""
+    """NB2 SVGP for one cell: (mean [ns,1], var [ns,1], params dict) for ``xs`` of
+    ns x 3, as the notebook's ``gp_sparse.predict_f(xs)``.  As in the notebook,
+    noise_variance None means 0.1 * var(y) and batchsize None means n.  The
+    returned dict is the trained model: predict_f / predict_y / elbo take it."""
     x = np.asarray(x, dtype=np.float64).reshape(-1, 3)
     y = np.asarray(y, dtype=np.float64).reshape(-1)
+    xs = np.asarray(xs, dtype=np.float64).reshape(-1, 3)
+    if len(xs) != 1:  # train once (the kernel's own predict sees the first target), then predict all
+        _, _, model = SVGP(x, y, xs[:1], Z, lengthscales, kernel_variance, noise_variance, mean,
+                           batchsize, iterations, seed)
+        m, v = predict_f(model, xs)
+        return m, v, model
     if noise_variance is None:
         noise_variance = 0.1 * np.var(y)
     if batchsize is None:
