@@ -30,17 +30,6 @@ c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
 
-# every symbol include/oi.h declares (tests/test_abi.py checks the export list)
-EXPORTS = ('oi_options_default', 'oi_gpr_batch', 'oi_nlml_grad_batch', 'oi_cg_create',
-           'oi_cg_step', 'oi_cg_feed', 'oi_cg_result', 'oi_cg_destroy', 'oi_last_error',
-           'oi_version', 'oi_profile_json', 'oi_profile_reset', 'oi_smooth_fields',
-           'oi_ball_query', 'oi_gather_rows', 'oi_nystrom_batch',
-           'oi_nystrom_fit_batch', 'oi_svgp_batch', 'oi_svgp_param_count', 'oi_session_create',
-           'oi_session_submit', 'oi_session_set_stream', 'oi_session_wait', 'oi_session_done',
-           'oi_session_destroy', 'oi_nystrom_session_create', 'oi_nystrom_session_submit',
-           'oi_nystrom_session_wait', 'oi_nystrom_session_destroy', 'oi_gpr_predict_multi',
-           'oi_svgp_predict', 'oi_svgp_elbo')
-
 
 class OiOptions(ctypes.Structure):
     _fields_ = [('device', ctypes.c_int32), ('maxiter', ctypes.c_int32), ('gtol', ctypes.c_double),
@@ -53,6 +42,54 @@ class OiError(RuntimeError):
     pass
 
 
+def _signatures():
+    D, L, I = c_double_p, c_int64_p, c_int32_p
+    f, l, i, u, n = ctypes.c_double, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int
+    H, S, O = ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(OiOptions)
+    fit = [D, D, L, l, L, L, D, D, f, D, I, I]   # the Nystrom fit's arguments up to info
+    gpr = [D, D, L, l, D, f, D, i, D, D, I, I]   # oi_gpr_batch's arguments up to info
+    return {
+        'oi_options_default': (None, [O]),
+        'oi_gpr_batch': (n, gpr + [O]),
+        'oi_gpr_predict_multi': (n, [D, D, L, l, D, L, f, D, D, D, D, D, I, O]),
+        'oi_nlml_grad_batch': (n, [D, D, D, L, l, D, D, D, I, O]),
+        'oi_cg_create': (H, [D, f, i]),
+        'oi_cg_step': (n, [H, D]),
+        'oi_cg_feed': (n, [H, f, D]),
+        'oi_cg_result': (n, [H, D, D, I, I, L, L, L]),
+        'oi_cg_destroy': (None, [H]),
+        'oi_last_error': (S, []),
+        'oi_version': (i, []),
+        'oi_profile_json': (l, [S, l]),
+        'oi_profile_reset': (None, []),
+        'oi_smooth_fields': (n, [D, i, l, l, D, D, f, D, i, D, O]),
+        'oi_ball_query': (n, [D, l, D, l, f, L, L, l, O]),
+        'oi_gather_rows': (n, [D, D, D, D, l, L, l, D, D, O]),
+        'oi_nystrom_batch': (n, [D, D, L, l, L, L, D, D, f, D, D, D, I, O]),
+        'oi_nystrom_fit_batch': (n, fit + [O]),
+        'oi_svgp_param_count': (i, [i]),
+        'oi_svgp_batch': (n, [D, D, L, l, D, i, D, i, i, i, u, f, D, D, D, D, I, O]),
+        'oi_svgp_predict': (n, [D, i, l, D, L, i, D, D, D, I, O]),
+        'oi_svgp_elbo': (n, [D, i, D, D, L, l, D, I, O]),
+        'oi_nystrom_session_create': (H, [O]),
+        'oi_nystrom_session_submit': (l, [H] + fit),
+        'oi_nystrom_session_wait': (n, [H, l]),
+        'oi_nystrom_session_destroy': (None, [H]),
+        'oi_session_create': (H, [O]),
+        'oi_session_submit': (l, [H] + gpr),
+        'oi_session_set_stream': (n, [H, H]),
+        'oi_session_wait': (n, [H, l]),
+        'oi_session_done': (n, [H, l]),
+        'oi_session_destroy': (None, [H]),
+    }
+
+
+# name -> (restype, argtypes) of every symbol include/oi.h declares; load()
+# applies it and tests/test_abi.py compares it with the header's prototypes
+SIGNATURES = _signatures()
+EXPORTS = tuple(SIGNATURES)
+
+
 def load():
     """Load liboi.so (once).  Raises OiError when it has not been built."""
     global _lib
@@ -62,109 +99,23 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise OiError(f"{LIB_PATH} not built: run `make -C {_HERE}` (or __graft_entry__.build())")
         lib = ctypes.CDLL(LIB_PATH)
-        lib.oi_options_default.argtypes = [ctypes.POINTER(OiOptions)]
-        lib.oi_options_default.restype = None
-        lib.oi_gpr_batch.argtypes = [c_double_p, c_double_p, c_int64_p, ctypes.c_int64, c_double_p,
-                                     ctypes.c_double, c_double_p, ctypes.c_int32, c_double_p,
-                                     c_double_p, c_int32_p, c_int32_p, ctypes.POINTER(OiOptions)]
-        lib.oi_gpr_batch.restype = ctypes.c_int
-        lib.oi_gpr_predict_multi.argtypes = [c_double_p, c_double_p, c_int64_p, ctypes.c_int64,
-                                             c_double_p, c_int64_p, ctypes.c_double, c_double_p,
-                                             c_double_p, c_double_p, c_double_p, c_double_p,
-                                             c_int32_p, ctypes.POINTER(OiOptions)]
-        lib.oi_gpr_predict_multi.restype = ctypes.c_int
-        lib.oi_nlml_grad_batch.argtypes = [c_double_p, c_double_p, c_double_p, c_int64_p,
-                                           ctypes.c_int64, c_double_p, c_double_p, c_double_p,
-                                           c_int32_p, ctypes.POINTER(OiOptions)]
-        lib.oi_nlml_grad_batch.restype = ctypes.c_int
-        lib.oi_cg_create.argtypes = [c_double_p, ctypes.c_double, ctypes.c_int32]
-        lib.oi_cg_create.restype = ctypes.c_void_p
-        lib.oi_cg_step.argtypes = [ctypes.c_void_p, c_double_p]
-        lib.oi_cg_step.restype = ctypes.c_int
-        lib.oi_cg_feed.argtypes = [ctypes.c_void_p, ctypes.c_double, c_double_p]
-        lib.oi_cg_feed.restype = ctypes.c_int
-        lib.oi_cg_result.argtypes = [ctypes.c_void_p, c_double_p, c_double_p, c_int32_p, c_int32_p,
-                                     c_int64_p, c_int64_p, c_int64_p]
-        lib.oi_cg_result.restype = ctypes.c_int
-        lib.oi_cg_destroy.argtypes = [ctypes.c_void_p]
-        lib.oi_cg_destroy.restype = None
-        lib.oi_last_error.argtypes = []
-        lib.oi_last_error.restype = ctypes.c_char_p
-        lib.oi_version.argtypes = []
-        lib.oi_version.restype = ctypes.c_int32
-        lib.oi_profile_json.argtypes = [ctypes.c_char_p, ctypes.c_int64]
-        lib.oi_profile_json.restype = ctypes.c_int64
-        lib.oi_profile_reset.argtypes = []
-        lib.oi_profile_reset.restype = None
-        lib.oi_smooth_fields.argtypes = [c_double_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
-                                         c_double_p, c_double_p, ctypes.c_double, c_double_p,
-                                         ctypes.c_int32, c_double_p, ctypes.POINTER(OiOptions)]
-        lib.oi_smooth_fields.restype = ctypes.c_int
-        lib.oi_ball_query.argtypes = [c_double_p, ctypes.c_int64, c_double_p, ctypes.c_int64,
-                                      ctypes.c_double, c_int64_p, c_int64_p, ctypes.c_int64,
-                                      ctypes.POINTER(OiOptions)]
-        lib.oi_ball_query.restype = ctypes.c_int
-        lib.oi_gather_rows.argtypes = [c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_int64,
-                                       c_int64_p, ctypes.c_int64, c_double_p, c_double_p,
-                                       ctypes.POINTER(OiOptions)]
-        lib.oi_gather_rows.restype = ctypes.c_int
-        lib.oi_nystrom_batch.argtypes = [c_double_p, c_double_p, c_int64_p, ctypes.c_int64,
-                                         c_int64_p, c_int64_p, c_double_p, c_double_p,
-                                         ctypes.c_double, c_double_p, c_double_p, c_double_p,
-                                         c_int32_p, ctypes.POINTER(OiOptions)]
-        lib.oi_nystrom_batch.restype = ctypes.c_int
-        lib.oi_nystrom_fit_batch.argtypes = [c_double_p, c_double_p, c_int64_p, ctypes.c_int64,
-                                             c_int64_p, c_int64_p, c_double_p, c_double_p,
-                                             ctypes.c_double, c_double_p, c_int32_p, c_int32_p,
-                                             ctypes.POINTER(OiOptions)]
-        lib.oi_nystrom_fit_batch.restype = ctypes.c_int
-        lib.oi_svgp_param_count.argtypes = [ctypes.c_int32]
-        lib.oi_svgp_param_count.restype = ctypes.c_int32
-        lib.oi_svgp_batch.argtypes = [c_double_p, c_double_p, c_int64_p, ctypes.c_int64, c_double_p,
-                                      ctypes.c_int32, c_double_p, ctypes.c_int32, ctypes.c_int32,
-                                      ctypes.c_int32, ctypes.c_uint64, ctypes.c_double, c_double_p,
-                                      c_double_p, c_double_p, c_double_p, c_int32_p,
-                                      ctypes.POINTER(OiOptions)]
-        lib.oi_svgp_batch.restype = ctypes.c_int
-        lib.oi_svgp_predict.argtypes = [c_double_p, ctypes.c_int32, ctypes.c_int64, c_double_p,
-                                        c_int64_p, ctypes.c_int32, c_double_p, c_double_p,
-                                        c_double_p, c_int32_p, ctypes.POINTER(OiOptions)]
-        lib.oi_svgp_predict.restype = ctypes.c_int
-        lib.oi_svgp_elbo.argtypes = [c_double_p, ctypes.c_int32, c_double_p, c_double_p, c_int64_p,
-                                     ctypes.c_int64, c_double_p, c_int32_p,
-                                     ctypes.POINTER(OiOptions)]
-        lib.oi_svgp_elbo.restype = ctypes.c_int
-        lib.oi_nystrom_session_create.argtypes = [ctypes.POINTER(OiOptions)]
-        lib.oi_nystrom_session_create.restype = ctypes.c_void_p
-        lib.oi_nystrom_session_submit.argtypes = [ctypes.c_void_p, c_double_p, c_double_p, c_int64_p,
-                                                  ctypes.c_int64, c_int64_p, c_int64_p, c_double_p,
-                                                  c_double_p, ctypes.c_double, c_double_p, c_int32_p,
-                                                  c_int32_p]
-        lib.oi_nystrom_session_submit.restype = ctypes.c_int64
-        lib.oi_nystrom_session_wait.argtypes = [ctypes.c_void_p, ctypes.c_int64]
-        lib.oi_nystrom_session_wait.restype = ctypes.c_int
-        lib.oi_nystrom_session_destroy.argtypes = [ctypes.c_void_p]
-        lib.oi_nystrom_session_destroy.restype = None
-        lib.oi_session_create.argtypes = [ctypes.POINTER(OiOptions)]
-        lib.oi_session_create.restype = ctypes.c_void_p
-        lib.oi_session_submit.argtypes = [ctypes.c_void_p, c_double_p, c_double_p, c_int64_p,
-                                          ctypes.c_int64, c_double_p, ctypes.c_double, c_double_p,
-                                          ctypes.c_int32, c_double_p, c_double_p, c_int32_p, c_int32_p]
-        lib.oi_session_submit.restype = ctypes.c_int64
-        lib.oi_session_set_stream.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        lib.oi_session_set_stream.restype = ctypes.c_int
-        lib.oi_session_wait.argtypes = [ctypes.c_void_p, ctypes.c_int64]
-        lib.oi_session_wait.restype = ctypes.c_int
-        lib.oi_session_done.argtypes = [ctypes.c_void_p, ctypes.c_int64]
-        lib.oi_session_done.restype = ctypes.c_int
-        lib.oi_session_destroy.argtypes = [ctypes.c_void_p]
-        lib.oi_session_destroy.restype = None
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
         return lib
 
 
-def _ptr(a, ctype):
+def _ptr(a, ctype=ctypes.c_double):
     return a.ctypes.data_as(ctypes.POINTER(ctype)) if a is not None else None
+
+
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _i64(a):
+    return np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
 
 
 def _check(rc):
@@ -187,51 +138,50 @@ def options(device=0, maxiter=-1, gtol=1e-5, stream=None, pool_bytes=0, max_pool
     return o
 
 
-def gpr_batch(xyt, z, offs, xs, mean, x0=None, opt=True, hyp=None, info=False, **opt_kw):
-    """oi_gpr_batch: returns (out [ncell x 8], status [ncell], info [ncell x 4] or None)."""
-    lib = load()
-    xyt = np.ascontiguousarray(xyt, dtype=np.float64).reshape(-1, 3)
-    z = np.ascontiguousarray(z, dtype=np.float64)
-    offs = np.ascontiguousarray(offs, dtype=np.int64)
-    xs = np.ascontiguousarray(xs, dtype=np.float64).reshape(-1, 3)
-    ncell = len(offs) - 1
-    if xs.shape[0] != ncell or offs[0] != 0 or offs[-1] != len(z) or xyt.shape[0] != len(z):
-        raise ValueError("inconsistent ragged batch")
-    out = np.empty((ncell, 8))
-    status = np.zeros(ncell, dtype=np.int32)
-    inf = np.zeros((ncell, 4), dtype=np.int32) if info else None
-    x0a = np.ascontiguousarray(x0, dtype=np.float64) if x0 is not None else None
-    hypa = np.ascontiguousarray(hyp, dtype=np.float64).reshape(-1, 5) if hyp is not None else None
-    if opt and (x0a is None or x0a.shape != (6,)):
-        raise ValueError("opt=True needs x0 of length 6")
-    if not opt and (hypa is None or hypa.shape[0] != ncell):
-        raise ValueError("opt=False needs hyp [ncell x 5]")
-    o = options(**opt_kw)
-    rc = lib.oi_gpr_batch(_ptr(xyt, ctypes.c_double), _ptr(z, ctypes.c_double),
-                          _ptr(offs, ctypes.c_int64), ncell, _ptr(xs, ctypes.c_double),
-                          float(mean), _ptr(x0a, ctypes.c_double), 1 if opt else 0,
-                          _ptr(hypa, ctypes.c_double), _ptr(out, ctypes.c_double),
-                          _ptr(status, ctypes.c_int32), _ptr(inf, ctypes.c_int32), ctypes.byref(o))
-    _check(rc)
-    return out, status, inf
-
-
 def _check_dev(t, device, dtype='float64', n=None, what='tensor'):
-    """A device tensor handed to liboi: right dtype, on cuda:<device>,
-    contiguous, ``n`` elements (liboi reads 8 bytes per element)."""
-    if str(t.dtype) != f'torch.{dtype}':
-        raise ValueError(f"{what} must be torch.{dtype}, got {t.dtype}")
-    if t.device.type != 'cuda' or (t.device.index if t.device.index is not None else 0) != int(device):
-        raise ValueError(f"{what} must live on cuda:{device}, got {t.device}")
+    """A device tensor handed to liboi: right dtype, on cuda:<device> (any
+    ordinal when ``device`` is None), contiguous, ``n`` elements (liboi reads
+    8 bytes per element)."""
+    if str(getattr(t, 'dtype', None)) != f'torch.{dtype}':
+        raise ValueError(f"{what} must be torch.{dtype}, got {getattr(t, 'dtype', type(t))}")
+    index = t.device.index if t.device.index is not None else 0
+    if t.device.type != 'cuda' or (device is not None and index != int(device)):
+        raise ValueError(f"{what} must live on cuda{'' if device is None else f':{device}'}, got {t.device}")
     if not t.is_contiguous():
         raise ValueError(f"{what} must be contiguous")
     if n is not None and t.numel() != n:
         raise ValueError(f"{what} has {t.numel()} elements, expected {n}")
 
 
+def _dptr(t, device, ctype=ctypes.c_double, n=None, what='tensor'):
+    """Device pointer of a torch tensor that passes _check_dev (fp64 or int64)."""
+    _check_dev(t, device, 'int64' if ctype is ctypes.c_int64 else 'float64', n, what)
+    return ctypes.cast(t.data_ptr(), ctypes.POINTER(ctype))
+
+
+def _obs(xyt, y, offs, device_inputs=False, device=0, what='y'):
+    """The observations of a ragged batch, ``xyt`` [N x 3] and ``y`` [N] cut by
+    ``offs`` (int64, from _i64): their two pointers and the objects that keep
+    them alive.  Host arrays become contiguous fp64 and must agree with
+    ``offs``; with ``device_inputs`` both are fp64 contiguous torch tensors on
+    cuda:``device`` with 3 N and N elements."""
+    if len(offs) == 0 or offs[0] != 0:
+        raise ValueError("inconsistent ragged batch")
+    N = int(offs[-1])
+    if device_inputs:
+        return (_dptr(xyt, device, n=3 * N, what='xyt'), _dptr(y, device, n=N, what=what), (xyt, y))
+    xyt = _f64(xyt).reshape(-1, 3)
+    y = _f64(y).reshape(-1)
+    if N != len(y) or xyt.shape[0] != len(y):
+        raise ValueError("inconsistent ragged batch")
+    return _ptr(xyt), _ptr(y), (xyt, y)
+
+
 def _sync_producers(device):
-    """The Nystrom / SVGP entry points run on private non-blocking streams:
-    wait here until torch's current stream has produced their device inputs."""
+    """The Nystrom entry points run on private non-blocking streams and the
+    SVGP ones on ``opts.stream`` (the NULL stream unless the caller sets it),
+    neither ordered after torch's current stream: wait here until that stream
+    has produced their device inputs."""
     import torch
     torch.cuda.current_stream(int(device)).synchronize()
 
@@ -244,55 +194,71 @@ def _caller_stream(device):
     return h or None
 
 
-def gpr_batch_device(xyt_dev, z_dev, offs, xs, mean, x0=None, opt=True, hyp=None, info=False,
-                     **opt_kw):
-    """oi_gpr_batch with inputs already resident in HBM: ``xyt_dev`` / ``z_dev``
-    are fp64 contiguous torch tensors on cuda:``opt_kw['device']``; the
-    metadata stays on the host.  Launches are ordered after torch's current
-    stream (include/oi.h, stream ordering)."""
-    lib = load()
-    offs = np.ascontiguousarray(offs, dtype=np.int64)
-    xs = np.ascontiguousarray(xs, dtype=np.float64).reshape(-1, 3)
-    ncell = len(offs) - 1
-    N = int(offs[-1])
-    dev = int(opt_kw.get('device', 0))
-    if xs.shape[0] != ncell or offs[0] != 0:
+def _gpr_args(xs, ncell, x0, opt, hyp):
+    """oi_gpr_batch's host metadata, checked: (xs [ncell x 3], x0 [6] | None, hyp [ncell x 5] | None)."""
+    xs = _f64(xs).reshape(-1, 3)
+    if xs.shape[0] != ncell:
         raise ValueError("inconsistent ragged batch")
-    _check_dev(xyt_dev, dev, n=3 * N, what='xyt')
-    _check_dev(z_dev, dev, n=N, what='z')
+    x0a = _f64(x0) if x0 is not None else None
+    hypa = _f64(hyp).reshape(-1, 5) if hyp is not None else None
+    if opt and (x0a is None or x0a.shape != (6,)):
+        raise ValueError("opt=True needs x0 of length 6")
+    if not opt and (hypa is None or hypa.shape[0] != ncell):
+        raise ValueError("opt=False needs hyp [ncell x 5]")
+    return xs, x0a, hypa
+
+
+def gpr_batch(xyt, z, offs, xs, mean, x0=None, opt=True, hyp=None, info=False, device_inputs=False,
+              **opt_kw):
+    """oi_gpr_batch: returns (out [ncell x 8], status [ncell], info [ncell x 4] or None).
+    With device_inputs=True ``xyt`` / ``z`` are fp64 contiguous torch tensors on
+    cuda:``device`` and the launches are ordered after torch's current stream
+    (include/oi.h, stream ordering); the metadata stays on the host."""
+    lib = load()
+    offs = _i64(offs)
+    ncell = len(offs) - 1
+    dev = int(opt_kw.get('device', 0))
+    xs, x0a, hypa = _gpr_args(xs, ncell, x0, opt, hyp)
+    px, pz, _keep = _obs(xyt, z, offs, device_inputs, dev, what='z')
+    if device_inputs:
+        opt_kw.setdefault('stream', _caller_stream(dev))
     out = np.empty((ncell, 8))
     status = np.zeros(ncell, dtype=np.int32)
     inf = np.zeros((ncell, 4), dtype=np.int32) if info else None
-    x0a = np.ascontiguousarray(x0, dtype=np.float64) if x0 is not None else None
-    hypa = np.ascontiguousarray(hyp, dtype=np.float64).reshape(-1, 5) if hyp is not None else None
-    opt_kw.setdefault('stream', _caller_stream(dev))
-    o = options(device_inputs=True, **opt_kw)
-    rc = lib.oi_gpr_batch(ctypes.cast(xyt_dev.data_ptr(), c_double_p),
-                          ctypes.cast(z_dev.data_ptr(), c_double_p),
-                          _ptr(offs, ctypes.c_int64), ncell, _ptr(xs, ctypes.c_double),
-                          float(mean), _ptr(x0a, ctypes.c_double), 1 if opt else 0,
-                          _ptr(hypa, ctypes.c_double), _ptr(out, ctypes.c_double),
-                          _ptr(status, ctypes.c_int32), _ptr(inf, ctypes.c_int32), ctypes.byref(o))
-    _check(rc)
+    o = options(device_inputs=device_inputs, **opt_kw)
+    _check(lib.oi_gpr_batch(px, pz, _ptr(offs, ctypes.c_int64), ncell, _ptr(xs), float(mean),
+                            _ptr(x0a), 1 if opt else 0, _ptr(hypa), _ptr(out),
+                            _ptr(status, ctypes.c_int32), _ptr(inf, ctypes.c_int32), ctypes.byref(o)))
     return out, status, inf
 
 
-def _multi_targets(offs, xs, toffs, hyp):
-    """Host metadata of oi_gpr_predict_multi, checked: (offs, xs, toffs, hyp, ncell)."""
-    offs = np.ascontiguousarray(offs, dtype=np.int64).reshape(-1)
-    toffs = np.ascontiguousarray(toffs, dtype=np.int64).reshape(-1)
-    xs = np.ascontiguousarray(xs, dtype=np.float64).reshape(-1, 3)
+def gpr_batch_device(xyt_dev, z_dev, offs, xs, mean, **kw):
+    """gpr_batch(..., device_inputs=True)."""
+    return gpr_batch(xyt_dev, z_dev, offs, xs, mean, device_inputs=True, **kw)
+
+
+def gpr_predict_multi(xyt, z, offs, xs, toffs, mean, hyp, cov=False, lz=True, device_inputs=False,
+                      **opt_kw):
+    """oi_gpr_predict_multi: predict every cell at its own list of targets
+    (``xs`` [T x 3], cell c owning rows toffs[c]:toffs[c+1]) at LINEAR hypers
+    ``hyp`` [ncell x 5].  Returns (fs [T], sd [T], lz [ncell] | None, cov | None,
+    status [ncell]); ``cov`` is the flat array of the cells' nt x nt posterior
+    covariances back to back (``split_cov`` cuts it up).  With
+    device_inputs=True ``xyt`` / ``z`` are fp64 contiguous torch tensors on
+    cuda:``device`` and the call runs on torch's current stream; targets,
+    offsets and hypers stay on the host."""
+    offs, toffs = _i64(offs), _i64(toffs)
+    xs = _f64(xs).reshape(-1, 3)
     ncell = len(offs) - 1
-    if ncell < 0 or len(toffs) != ncell + 1 or offs[0] != 0 or toffs[0] != 0 \
-            or toffs[-1] != xs.shape[0]:
+    if len(toffs) != ncell + 1 or toffs[0] != 0 or toffs[-1] != xs.shape[0]:
         raise ValueError("inconsistent ragged batch")
-    hyp = np.ascontiguousarray(hyp, dtype=np.float64).reshape(-1, 5)
+    hyp = _f64(hyp).reshape(-1, 5)
     if hyp.shape[0] != ncell:
         raise ValueError("hyp must be [ncell x 5]")
-    return offs, xs, toffs, hyp, ncell
-
-
-def _predict_multi(px, pz, offs, xs, toffs, mean, hyp, ncell, cov, lz, o):
+    dev = int(opt_kw.get('device', 0))
+    px, pz, _keep = _obs(xyt, z, offs, device_inputs, dev, what='z')
+    if device_inputs:
+        opt_kw.setdefault('stream', _caller_stream(dev))
     T = int(toffs[-1])
     fs = np.empty(T)
     sd = np.empty(T)
@@ -300,45 +266,17 @@ def _predict_multi(px, pz, offs, xs, toffs, mean, hyp, ncell, cov, lz, o):
     nt = np.diff(toffs)
     cova = np.empty(int((nt * nt).sum())) if cov else None
     status = np.zeros(ncell, dtype=np.int32)
-    rc = load().oi_gpr_predict_multi(px, pz, _ptr(offs, ctypes.c_int64), ncell,
-                                     _ptr(xs, ctypes.c_double), _ptr(toffs, ctypes.c_int64),
-                                     float(mean), _ptr(hyp, ctypes.c_double),
-                                     _ptr(fs, ctypes.c_double), _ptr(sd, ctypes.c_double),
-                                     _ptr(lza, ctypes.c_double), _ptr(cova, ctypes.c_double),
-                                     _ptr(status, ctypes.c_int32), ctypes.byref(o))
-    _check(rc)
+    o = options(device_inputs=device_inputs, **opt_kw)
+    _check(load().oi_gpr_predict_multi(px, pz, _ptr(offs, ctypes.c_int64), ncell, _ptr(xs),
+                                       _ptr(toffs, ctypes.c_int64), float(mean), _ptr(hyp), _ptr(fs),
+                                       _ptr(sd), _ptr(lza), _ptr(cova), _ptr(status, ctypes.c_int32),
+                                       ctypes.byref(o)))
     return fs, sd, lza, cova, status
 
 
-def gpr_predict_multi(xyt, z, offs, xs, toffs, mean, hyp, cov=False, lz=True, **opt_kw):
-    """oi_gpr_predict_multi: predict every cell at its own list of targets
-    (``xs`` [T x 3], cell c owning rows toffs[c]:toffs[c+1]) at LINEAR hypers
-    ``hyp`` [ncell x 5].  Returns (fs [T], sd [T], lz [ncell] | None, cov | None,
-    status [ncell]); ``cov`` is the flat array of the cells' nt x nt posterior
-    covariances back to back (``split_cov`` cuts it up)."""
-    offs, xs, toffs, hyp, ncell = _multi_targets(offs, xs, toffs, hyp)
-    xyt = np.ascontiguousarray(xyt, dtype=np.float64).reshape(-1, 3)
-    z = np.ascontiguousarray(z, dtype=np.float64).reshape(-1)
-    if offs[-1] != len(z) or xyt.shape[0] != len(z):
-        raise ValueError("inconsistent ragged batch")
-    return _predict_multi(_ptr(xyt, ctypes.c_double), _ptr(z, ctypes.c_double), offs, xs, toffs,
-                          mean, hyp, ncell, cov, lz, options(**opt_kw))
-
-
-def gpr_predict_multi_device(xyt_dev, z_dev, offs, xs, toffs, mean, hyp, cov=False, lz=True,
-                             **opt_kw):
-    """gpr_predict_multi with ``xyt_dev`` / ``z_dev`` already resident in HBM
-    (fp64 contiguous torch tensors on cuda:``opt_kw['device']``); targets,
-    offsets and hypers stay on the host.  Runs on torch's current stream."""
-    offs, xs, toffs, hyp, ncell = _multi_targets(offs, xs, toffs, hyp)
-    N = int(offs[-1])
-    dev = int(opt_kw.get('device', 0))
-    _check_dev(xyt_dev, dev, n=3 * N, what='xyt')
-    _check_dev(z_dev, dev, n=N, what='z')
-    opt_kw.setdefault('stream', _caller_stream(dev))
-    return _predict_multi(ctypes.cast(xyt_dev.data_ptr(), c_double_p),
-                          ctypes.cast(z_dev.data_ptr(), c_double_p), offs, xs, toffs, mean, hyp,
-                          ncell, cov, lz, options(device_inputs=True, **opt_kw))
+def gpr_predict_multi_device(xyt_dev, z_dev, offs, xs, toffs, mean, hyp, **kw):
+    """gpr_predict_multi(..., device_inputs=True)."""
+    return gpr_predict_multi(xyt_dev, z_dev, offs, xs, toffs, mean, hyp, device_inputs=True, **kw)
 
 
 def split_cov(cov, toffs):
@@ -348,7 +286,56 @@ def split_cov(cov, toffs):
     return [cov[o[c]:o[c + 1]].reshape(nt[c], nt[c]) for c in range(len(nt))]
 
 
-class Session:
+class _SessionBase:
+    """What oi_session_* and oi_nystrom_session_* share: the handle, the
+    tickets in flight with the arrays they keep alive, wait(ticket), close."""
+    _PREFIX = None
+
+    def __init__(self, device=0, device_inputs=False, **opt_kw):
+        self._lib = load()
+        self.device = int(device)
+        self.device_inputs = bool(device_inputs)
+        self._opts = options(device=device, device_inputs=device_inputs, **opt_kw)
+        self._h = self._fn('create')(ctypes.byref(self._opts))
+        if not self._h:
+            raise OiError(f"{self._PREFIX}_create: {self._lib.oi_last_error().decode(errors='replace')}")
+        self._live = {}    # ticket -> (out, status, info, inputs kept alive), not yet complete
+
+    def _fn(self, verb):
+        return getattr(self._lib, f'{self._PREFIX}_{verb}')
+
+    def _ticket(self, t, out, status, info, keep):
+        if t < 0:
+            _check(int(t))
+        # device inputs and the outputs must outlive the ticket
+        self._live[int(t)] = (out, status, info, keep)
+        return int(t)
+
+    def wait(self, ticket):
+        """Block until ``ticket`` completes and return its (out, status, info)."""
+        ticket = int(ticket)
+        if ticket not in self._live:
+            raise KeyError(f"unknown or already collected session ticket {ticket}")
+        _check(self._fn('wait')(self._h, ticket))
+        return self._live.pop(ticket)[:3]
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self._fn('destroy')(self._h)
+            self._h = None
+            self._live.clear()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+class Session(_SessionBase):
     """oi_session_*: continuous batching across calls (include/oi.h).
 
     ``submit`` takes the oi_gpr_batch arguments (host numpy arrays, or fp64
@@ -362,57 +349,28 @@ class Session:
     (oi_session_set_stream), so a producer running under another
     ``torch.cuda.stream(...)`` context is waited for.  Results of a ticket are
     collected once: by ``wait(ticket)``, or in the dict ``wait()`` returns."""
+    _PREFIX = 'oi_session'
 
     def __init__(self, device=0, device_inputs=False, **opt_kw):
-        self._lib = load()
-        self.device = int(device)
-        self.device_inputs = bool(device_inputs)
-        if self.device_inputs:
-            opt_kw.setdefault('stream', _caller_stream(self.device))
-        self._opts = options(device=device, device_inputs=device_inputs, **opt_kw)
-        self._h = self._lib.oi_session_create(ctypes.byref(self._opts))
-        if not self._h:
-            raise OiError(f"oi_session_create: {self._lib.oi_last_error().decode(errors='replace')}")
-        self._live = {}    # ticket -> results (and the inputs they keep alive), not yet complete
+        if device_inputs:
+            opt_kw.setdefault('stream', _caller_stream(int(device)))
+        super().__init__(device, device_inputs, **opt_kw)
         self._done = {}    # ticket -> results completed by wait(-1), not yet collected
 
     def submit(self, xyt, z, offs, xs, mean, x0=None, opt=True, hyp=None):
-        offs = np.ascontiguousarray(offs, dtype=np.int64)
-        xs = np.ascontiguousarray(xs, dtype=np.float64).reshape(-1, 3)
+        offs = _i64(offs)
         ncell = len(offs) - 1
-        N = int(offs[-1]) if ncell >= 0 else 0
-        if xs.shape[0] != ncell or offs[0] != 0:
-            raise ValueError("inconsistent ragged batch")
+        xs, x0a, hypa = _gpr_args(xs, ncell, x0, opt, hyp)
+        px, pz, keep = _obs(xyt, z, offs, self.device_inputs, self.device, what='z')
         if self.device_inputs:
-            _check_dev(xyt, self.device, n=3 * N, what='xyt')
-            _check_dev(z, self.device, n=N, what='z')
-            px, pz = _dptr(xyt), _dptr(z)
             _check(self._lib.oi_session_set_stream(self._h, _caller_stream(self.device)))
-        else:
-            xyt = np.ascontiguousarray(xyt, dtype=np.float64).reshape(-1, 3)
-            z = np.ascontiguousarray(z, dtype=np.float64)
-            if xyt.shape[0] != N or len(z) != N:
-                raise ValueError("inconsistent ragged batch")
-            px, pz = _ptr(xyt, ctypes.c_double), _ptr(z, ctypes.c_double)
-        x0a = np.ascontiguousarray(x0, dtype=np.float64) if x0 is not None else None
-        hypa = np.ascontiguousarray(hyp, dtype=np.float64).reshape(-1, 5) if hyp is not None else None
-        if opt and (x0a is None or x0a.shape != (6,)):
-            raise ValueError("opt=True needs x0 of length 6")
-        if not opt and (hypa is None or hypa.shape[0] != ncell):
-            raise ValueError("opt=False needs hyp [ncell x 5]")
         out = np.empty((ncell, 8))
         status = np.zeros(ncell, dtype=np.int32)
         info = np.zeros((ncell, 4), dtype=np.int32)
-        t = self._lib.oi_session_submit(self._h, px, pz, _ptr(offs, ctypes.c_int64), ncell,
-                                        _ptr(xs, ctypes.c_double), float(mean),
-                                        _ptr(x0a, ctypes.c_double), 1 if opt else 0,
-                                        _ptr(hypa, ctypes.c_double), _ptr(out, ctypes.c_double),
+        t = self._lib.oi_session_submit(self._h, px, pz, _ptr(offs, ctypes.c_int64), ncell, _ptr(xs),
+                                        float(mean), _ptr(x0a), 1 if opt else 0, _ptr(hypa), _ptr(out),
                                         _ptr(status, ctypes.c_int32), _ptr(info, ctypes.c_int32))
-        if t < 0:
-            _check(int(t))
-        # device inputs and the outputs must outlive the ticket
-        self._live[int(t)] = (out, status, info, xyt, z)
-        return int(t)
+        return self._ticket(t, out, status, info, keep)
 
     def done(self, ticket):
         return self._lib.oi_session_done(self._h, int(ticket)) == 1
@@ -423,59 +381,46 @@ class Session:
         ``{ticket: (out, status, info)}`` for every ticket not collected yet
         (those can still be collected one by one with ``wait(ticket)``)."""
         ticket = int(ticket)
+        if ticket in self._done:
+            return self._done.pop(ticket)
         if ticket >= 0:
-            if ticket in self._done:
-                return self._done.pop(ticket)
-            if ticket not in self._live:
-                raise KeyError(f"unknown or already collected session ticket {ticket}")
+            return super().wait(ticket)
         _check(self._lib.oi_session_wait(self._h, ticket))
-        if ticket < 0:
-            for t, (out, status, info, _, _) in self._live.items():
-                self._done[t] = (out, status, info)
-            self._live.clear()
-            return dict(self._done)
-        out, status, info, _, _ = self._live.pop(ticket)
-        return out, status, info
+        for t, r in self._live.items():
+            self._done[t] = r[:3]
+        self._live.clear()
+        return dict(self._done)
 
     def close(self):
-        if getattr(self, '_h', None):
-            self._lib.oi_session_destroy(self._h)
-            self._h = None
-            self._live.clear()
-            self._done.clear()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
+        super().close()
+        self._done = {}
 
 
 def nlml_grad_batch(xyt, y, mX, offs, h, **opt_kw):
     """oi_nlml_grad_batch: returns (nlz [ncell], grad [ncell x 6], status [ncell])."""
     lib = load()
-    xyt = np.ascontiguousarray(xyt, dtype=np.float64).reshape(-1, 3)
-    y = np.ascontiguousarray(y, dtype=np.float64)
-    mX = np.ascontiguousarray(mX, dtype=np.float64)
-    offs = np.ascontiguousarray(offs, dtype=np.int64)
-    h = np.ascontiguousarray(h, dtype=np.float64).reshape(-1, 6)
+    offs = _i64(offs)
+    px, py, _keep = _obs(xyt, y, offs)
+    mX = _f64(mX)
+    h = _f64(h).reshape(-1, 6)
     ncell = len(offs) - 1
-    if h.shape[0] != ncell or offs[-1] != len(y) or len(mX) != len(y) or xyt.shape[0] != len(y):
+    if h.shape[0] != ncell or len(mX) != offs[-1]:
         raise ValueError("inconsistent ragged batch")
     nlz = np.empty(ncell)
     grad = np.empty((ncell, 6))
     status = np.zeros(ncell, dtype=np.int32)
     o = options(**opt_kw)
-    rc = lib.oi_nlml_grad_batch(_ptr(xyt, ctypes.c_double), _ptr(y, ctypes.c_double),
-                                _ptr(mX, ctypes.c_double), _ptr(offs, ctypes.c_int64), ncell,
-                                _ptr(h, ctypes.c_double), _ptr(nlz, ctypes.c_double),
-                                _ptr(grad, ctypes.c_double), _ptr(status, ctypes.c_int32),
-                                ctypes.byref(o))
-    _check(rc)
+    _check(lib.oi_nlml_grad_batch(px, py, _ptr(mX), _ptr(offs, ctypes.c_int64), ncell, _ptr(h),
+                                  _ptr(nlz), _ptr(grad), _ptr(status, ctypes.c_int32), ctypes.byref(o)))
     return nlz, grad, status
+
+
+def _inducing(sel, soffs, ncell, what="inconsistent inducing rows"):
+    """The ragged inducing rows (0-based within each cell), checked against ncell."""
+    sel, soffs = _i64(sel), _i64(soffs)
+    if len(soffs) != ncell + 1 or soffs[-1] != len(sel):
+        raise ValueError(what)
+    return sel, soffs
 
 
 def nystrom_batch(xyt, y, offs, sel, soffs, hyp, xs=None, mean=0.0, objective=True,
@@ -485,32 +430,38 @@ def nystrom_batch(xyt, y, offs, sel, soffs, hyp, xs=None, mean=0.0, objective=Tr
     (ell_x, ell_y, ell_t, sf2, sn2) per cell; ``sel``/``soffs`` the ragged
     inducing rows (0-based within each cell)."""
     lib = load()
-    xyt = np.ascontiguousarray(xyt, dtype=np.float64).reshape(-1, 3)
-    y = np.ascontiguousarray(y, dtype=np.float64)
-    offs = np.ascontiguousarray(offs, dtype=np.int64)
-    sel = np.ascontiguousarray(sel, dtype=np.int64)
-    soffs = np.ascontiguousarray(soffs, dtype=np.int64)
+    offs = _i64(offs)
     ncell = len(offs) - 1
-    hyp = np.ascontiguousarray(hyp, dtype=np.float64).reshape(ncell, 5)
-    if offs[-1] != len(y) or xyt.shape[0] != len(y) or len(soffs) != ncell + 1 \
-            or soffs[-1] != len(sel):
-        raise ValueError("inconsistent ragged batch")
-    if predict:
-        xs = np.ascontiguousarray(xs, dtype=np.float64).reshape(ncell, 3)
+    px, py, _keep = _obs(xyt, y, offs)
+    hyp = _f64(hyp).reshape(ncell, 5)
+    sel, soffs = _inducing(sel, soffs, ncell, "inconsistent ragged batch")
+    xs = _f64(xs).reshape(ncell, 3) if predict else None
     nlz = np.empty(ncell) if objective else None
     grad = np.empty((ncell, 5)) if objective else None
     pred = np.empty((ncell, 3)) if predict else None
     status = np.zeros(ncell, dtype=np.int32)
     o = options(**opt_kw)
-    rc = lib.oi_nystrom_batch(_ptr(xyt, ctypes.c_double), _ptr(y, ctypes.c_double),
-                              _ptr(offs, ctypes.c_int64), ncell, _ptr(sel, ctypes.c_int64),
-                              _ptr(soffs, ctypes.c_int64), _ptr(hyp, ctypes.c_double),
-                              _ptr(xs if predict else None, ctypes.c_double), float(mean),
-                              _ptr(nlz, ctypes.c_double), _ptr(grad, ctypes.c_double),
-                              _ptr(pred, ctypes.c_double), _ptr(status, ctypes.c_int32),
-                              ctypes.byref(o))
-    _check(rc)
+    _check(lib.oi_nystrom_batch(px, py, _ptr(offs, ctypes.c_int64), ncell, _ptr(sel, ctypes.c_int64),
+                                _ptr(soffs, ctypes.c_int64), _ptr(hyp), _ptr(xs), float(mean),
+                                _ptr(nlz), _ptr(grad), _ptr(pred), _ptr(status, ctypes.c_int32),
+                                ctypes.byref(o)))
     return nlz, grad, pred, status
+
+
+def _nystrom_fit_args(xyt, y, offs, sel, soffs, x0, xs, device_inputs, device):
+    """What oi_nystrom_fit_batch and oi_nystrom_session_submit both take, checked:
+    the leading C arguments up to ``xs``, ncell, and the inputs to keep alive."""
+    offs = _i64(offs)
+    ncell = len(offs) - 1
+    x0 = _f64(x0).reshape(5)
+    xs = _f64(xs).reshape(ncell, 3)
+    px, py, keep = _obs(xyt, y, offs, device_inputs, device)
+    if device_inputs:
+        _sync_producers(device)
+    sel, soffs = _inducing(sel, soffs, ncell)
+    args = (px, py, _ptr(offs, ctypes.c_int64), ncell, _ptr(sel, ctypes.c_int64),
+            _ptr(soffs, ctypes.c_int64), _ptr(x0), _ptr(xs))
+    return args, ncell, (keep, offs, sel, soffs, x0, xs)
 
 
 def nystrom_fit_batch(xyt, y, offs, sel, soffs, x0, xs, mean, **opt_kw):
@@ -518,111 +469,35 @@ def nystrom_fit_batch(xyt, y, offs, sel, soffs, x0, xs, mean, **opt_kw):
     hypers), status [ncell], info [ncell x 4]).  With device_inputs=True, xyt
     and y are torch device tensors."""
     lib = load()
-    offs = np.ascontiguousarray(offs, dtype=np.int64)
-    sel = np.ascontiguousarray(sel, dtype=np.int64)
-    soffs = np.ascontiguousarray(soffs, dtype=np.int64)
-    ncell = len(offs) - 1
-    x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(5)
-    xs = np.ascontiguousarray(xs, dtype=np.float64).reshape(ncell, 3)
-    if opt_kw.get('device_inputs'):
-        if xyt.numel() != 3 * offs[-1] or y.numel() != offs[-1]:
-            raise ValueError("inconsistent ragged batch")
-        px, py = _dptr(xyt), _dptr(y)
-        _sync_producers(opt_kw.get('device', 0))
-    else:
-        xyt = np.ascontiguousarray(xyt, dtype=np.float64).reshape(-1, 3)
-        y = np.ascontiguousarray(y, dtype=np.float64)
-        if offs[-1] != len(y) or xyt.shape[0] != len(y):
-            raise ValueError("inconsistent ragged batch")
-        px, py = _ptr(xyt, ctypes.c_double), _ptr(y, ctypes.c_double)
-    if len(soffs) != ncell + 1 or soffs[-1] != len(sel):
-        raise ValueError("inconsistent inducing rows")
+    args, ncell, _keep = _nystrom_fit_args(xyt, y, offs, sel, soffs, x0, xs,
+                                           opt_kw.get('device_inputs'), opt_kw.get('device', 0))
     out = np.empty((ncell, 8))
     status = np.zeros(ncell, dtype=np.int32)
     info = np.zeros((ncell, 4), dtype=np.int32)
     o = options(**opt_kw)
-    rc = lib.oi_nystrom_fit_batch(px, py, _ptr(offs, ctypes.c_int64), ncell,
-                                  _ptr(sel, ctypes.c_int64), _ptr(soffs, ctypes.c_int64),
-                                  _ptr(x0, ctypes.c_double), _ptr(xs, ctypes.c_double), float(mean),
-                                  _ptr(out, ctypes.c_double), _ptr(status, ctypes.c_int32),
-                                  _ptr(info, ctypes.c_int32), ctypes.byref(o))
-    _check(rc)
+    _check(lib.oi_nystrom_fit_batch(*args, float(mean), _ptr(out), _ptr(status, ctypes.c_int32),
+                                    _ptr(info, ctypes.c_int32), ctypes.byref(o)))
     return out, status, info
 
 
-class NystromSession:
+class NystromSession(_SessionBase):
     """oi_nystrom_session_*: Nystrom fits (oi_nystrom_fit_batch) as a stream of
     batches with continuous batching across calls.  ``submit`` takes
     nystrom_fit_batch's arguments and returns a ticket; ``wait(ticket)``
     returns that batch's (out, status, info) once its last cell is fitted and
     predicted.  Device inputs (``device_inputs=True``) must stay alive until
     their ticket completes (the session keeps a reference)."""
-
-    def __init__(self, device=0, device_inputs=False, **opt_kw):
-        self._lib = load()
-        self.device = int(device)
-        self.device_inputs = bool(device_inputs)
-        self._opts = options(device=device, device_inputs=device_inputs, **opt_kw)
-        self._h = self._lib.oi_nystrom_session_create(ctypes.byref(self._opts))
-        if not self._h:
-            raise OiError(f"oi_nystrom_session_create: {self._lib.oi_last_error().decode(errors='replace')}")
-        self._live = {}
+    _PREFIX = 'oi_nystrom_session'
 
     def submit(self, xyt, y, offs, sel, soffs, x0, xs, mean):
-        offs = np.ascontiguousarray(offs, dtype=np.int64)
-        sel = np.ascontiguousarray(sel, dtype=np.int64)
-        soffs = np.ascontiguousarray(soffs, dtype=np.int64)
-        ncell = len(offs) - 1
-        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(5)
-        xs = np.ascontiguousarray(xs, dtype=np.float64).reshape(ncell, 3)
-        if self.device_inputs:
-            _check_dev(xyt, self.device, n=3 * int(offs[-1]), what='xyt')
-            _check_dev(y, self.device, n=int(offs[-1]), what='y')
-            px, py = _dptr(xyt), _dptr(y)
-            _sync_producers(self.device)
-        else:
-            xyt = np.ascontiguousarray(xyt, dtype=np.float64).reshape(-1, 3)
-            y = np.ascontiguousarray(y, dtype=np.float64)
-            if offs[-1] != len(y) or xyt.shape[0] != len(y):
-                raise ValueError("inconsistent ragged batch")
-            px, py = _ptr(xyt, ctypes.c_double), _ptr(y, ctypes.c_double)
-        if len(soffs) != ncell + 1 or soffs[-1] != len(sel):
-            raise ValueError("inconsistent inducing rows")
+        args, ncell, keep = _nystrom_fit_args(xyt, y, offs, sel, soffs, x0, xs, self.device_inputs,
+                                              self.device)
         out = np.empty((ncell, 8))
         status = np.zeros(ncell, dtype=np.int32)
         info = np.zeros((ncell, 4), dtype=np.int32)
-        t = self._lib.oi_nystrom_session_submit(self._h, px, py, _ptr(offs, ctypes.c_int64), ncell,
-                                                _ptr(sel, ctypes.c_int64), _ptr(soffs, ctypes.c_int64),
-                                                _ptr(x0, ctypes.c_double), _ptr(xs, ctypes.c_double),
-                                                float(mean), _ptr(out, ctypes.c_double),
+        t = self._lib.oi_nystrom_session_submit(self._h, *args, float(mean), _ptr(out),
                                                 _ptr(status, ctypes.c_int32), _ptr(info, ctypes.c_int32))
-        if t < 0:
-            _check(int(t))
-        self._live[int(t)] = (out, status, info, xyt, y)
-        return int(t)
-
-    def wait(self, ticket):
-        ticket = int(ticket)
-        if ticket not in self._live:
-            raise KeyError(f"unknown or already collected session ticket {ticket}")
-        _check(self._lib.oi_nystrom_session_wait(self._h, ticket))
-        out, status, info, _, _ = self._live.pop(ticket)
-        return out, status, info
-
-    def close(self):
-        if getattr(self, '_h', None):
-            self._lib.oi_nystrom_session_destroy(self._h)
-            self._h = None
-            self._live.clear()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
+        return self._ticket(t, out, status, info, keep)
 
 
 def svgp_batch(xyt, y, offs, Z0, init, xs, batch=100, iterations=10000, log_every=10, seed=0,
@@ -631,23 +506,15 @@ def svgp_batch(xyt, y, offs, Z0, init, xs, batch=100, iterations=10000, log_ever
     params [ncell x P] or None, elbo [ncell x nlog] or None).
     Z0 [ncell x M x 3]; init [ncell x 6] = (ls_x, ls_y, ls_t, kernel var, noise var, mean)."""
     lib = load()
-    offs = np.ascontiguousarray(offs, dtype=np.int64)
+    offs = _i64(offs)
     ncell = len(offs) - 1
-    Z0 = np.ascontiguousarray(Z0, dtype=np.float64).reshape(ncell, -1, 3)
+    Z0 = _f64(Z0).reshape(ncell, -1, 3)
     M = Z0.shape[1]
-    init = np.ascontiguousarray(init, dtype=np.float64).reshape(ncell, 6)
-    xs = np.ascontiguousarray(xs, dtype=np.float64).reshape(ncell, 3)
+    init = _f64(init).reshape(ncell, 6)
+    xs = _f64(xs).reshape(ncell, 3)
+    px, py, _keep = _obs(xyt, y, offs, opt_kw.get('device_inputs'), opt_kw.get('device', 0))
     if opt_kw.get('device_inputs'):
-        if xyt.numel() != 3 * offs[-1] or y.numel() != offs[-1]:
-            raise ValueError("inconsistent ragged batch")
-        px, py = _dptr(xyt), _dptr(y)
         _sync_producers(opt_kw.get('device', 0))
-    else:
-        xyt = np.ascontiguousarray(xyt, dtype=np.float64).reshape(-1, 3)
-        y = np.ascontiguousarray(y, dtype=np.float64)
-        if offs[-1] != len(y) or xyt.shape[0] != len(y):
-            raise ValueError("inconsistent ragged batch")
-        px, py = _ptr(xyt, ctypes.c_double), _ptr(y, ctypes.c_double)
     P = int(lib.oi_svgp_param_count(M))
     nlog = (iterations + log_every - 1) // log_every if log_every else 0
     pred = np.empty((ncell, 2))
@@ -655,18 +522,16 @@ def svgp_batch(xyt, y, offs, Z0, init, xs, batch=100, iterations=10000, log_ever
     params = np.empty((ncell, P)) if want_params else None
     elbo = np.empty((ncell, nlog)) if nlog else None
     o = options(**opt_kw)
-    rc = lib.oi_svgp_batch(px, py, _ptr(offs, ctypes.c_int64), ncell, _ptr(Z0, ctypes.c_double), M,
-                           _ptr(init, ctypes.c_double), int(batch), int(iterations), int(log_every),
-                           int(seed), float(lr), _ptr(xs, ctypes.c_double), _ptr(pred, ctypes.c_double),
-                           _ptr(params, ctypes.c_double), _ptr(elbo, ctypes.c_double),
-                           _ptr(status, ctypes.c_int32), ctypes.byref(o))
-    _check(rc)
+    _check(lib.oi_svgp_batch(px, py, _ptr(offs, ctypes.c_int64), ncell, _ptr(Z0), M, _ptr(init),
+                             int(batch), int(iterations), int(log_every), int(seed), float(lr),
+                             _ptr(xs), _ptr(pred), _ptr(params), _ptr(elbo),
+                             _ptr(status, ctypes.c_int32), ctypes.byref(o)))
     return pred, status, params, elbo
 
 
 def _svgp_rows(params):
     """``params`` as [ncell x P] rows and the M that P = 6 + 4 M + M (M + 1) / 2 belongs to."""
-    params = np.ascontiguousarray(params, dtype=np.float64)
+    params = _f64(params)
     if params.ndim == 1:
         params = params[None]
     if params.ndim != 2:
@@ -687,31 +552,27 @@ def svgp_predict(params, xs, toffs, with_noise=False, cov=False, **opt_kw):
     lib = load()
     params, M = _svgp_rows(params)
     ncell = params.shape[0]
-    toffs = np.ascontiguousarray(toffs, dtype=np.int64).reshape(-1)
+    toffs = _i64(toffs)
     if len(toffs) != ncell + 1 or toffs[0] != 0 or np.any(np.diff(toffs) < 0):
         raise ValueError("inconsistent ragged batch")
     T = int(toffs[-1])
     if opt_kw.get('device_inputs'):
-        if xs.numel() != 3 * T:
-            raise ValueError("inconsistent ragged batch")
-        pxs = _dptr(xs)
+        pxs = _dptr(xs, opt_kw.get('device', 0), n=3 * T, what='xs')
         _sync_producers(opt_kw.get('device', 0))
     else:
-        xs = np.ascontiguousarray(xs, dtype=np.float64).reshape(-1, 3)
+        xs = _f64(xs).reshape(-1, 3)
         if xs.shape[0] != T:
             raise ValueError("inconsistent ragged batch")
-        pxs = _ptr(xs, ctypes.c_double)
+        pxs = _ptr(xs)
     mean = np.empty(T)
     var = np.empty(T)
     nt = np.diff(toffs)
     cova = np.empty(int((nt * nt).sum())) if cov else None
     status = np.zeros(ncell, dtype=np.int32)
     o = options(**opt_kw)
-    _check(lib.oi_svgp_predict(_ptr(params, ctypes.c_double), M, ncell, pxs,
-                               _ptr(toffs, ctypes.c_int64), 1 if with_noise else 0,
-                               _ptr(mean, ctypes.c_double), _ptr(var, ctypes.c_double),
-                               _ptr(cova, ctypes.c_double), _ptr(status, ctypes.c_int32),
-                               ctypes.byref(o)))
+    _check(lib.oi_svgp_predict(_ptr(params), M, ncell, pxs, _ptr(toffs, ctypes.c_int64),
+                               1 if with_noise else 0, _ptr(mean), _ptr(var), _ptr(cova),
+                               _ptr(status, ctypes.c_int32), ctypes.byref(o)))
     return mean, var, cova, status
 
 
@@ -722,26 +583,17 @@ def svgp_elbo(params, xyt, y, offs, **opt_kw):
     lib = load()
     params, M = _svgp_rows(params)
     ncell = params.shape[0]
-    offs = np.ascontiguousarray(offs, dtype=np.int64).reshape(-1)
-    if len(offs) != ncell + 1 or offs[0] != 0:
+    offs = _i64(offs)
+    if len(offs) != ncell + 1:
         raise ValueError("inconsistent ragged batch")
+    px, py, _keep = _obs(xyt, y, offs, opt_kw.get('device_inputs'), opt_kw.get('device', 0))
     if opt_kw.get('device_inputs'):
-        if xyt.numel() != 3 * offs[-1] or y.numel() != offs[-1]:
-            raise ValueError("inconsistent ragged batch")
-        px, py = _dptr(xyt), _dptr(y)
         _sync_producers(opt_kw.get('device', 0))
-    else:
-        xyt = np.ascontiguousarray(xyt, dtype=np.float64).reshape(-1, 3)
-        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
-        if offs[-1] != len(y) or xyt.shape[0] != len(y):
-            raise ValueError("inconsistent ragged batch")
-        px, py = _ptr(xyt, ctypes.c_double), _ptr(y, ctypes.c_double)
     elbo = np.empty(ncell)
     status = np.zeros(ncell, dtype=np.int32)
     o = options(**opt_kw)
-    _check(lib.oi_svgp_elbo(_ptr(params, ctypes.c_double), M, px, py, _ptr(offs, ctypes.c_int64),
-                            ncell, _ptr(elbo, ctypes.c_double), _ptr(status, ctypes.c_int32),
-                            ctypes.byref(o)))
+    _check(lib.oi_svgp_elbo(_ptr(params), M, px, py, _ptr(offs, ctypes.c_int64), ncell, _ptr(elbo),
+                            _ptr(status, ctypes.c_int32), ctypes.byref(o)))
     return elbo, status
 
 
@@ -750,22 +602,22 @@ class CG:
 
     def __init__(self, x0, gtol=1e-5, maxiter=-1):
         self._lib = load()
-        x0 = np.ascontiguousarray(x0, dtype=np.float64)
-        self._h = self._lib.oi_cg_create(_ptr(x0, ctypes.c_double), float(gtol), int(maxiter))
+        x0 = _f64(x0)
+        self._h = self._lib.oi_cg_create(_ptr(x0), float(gtol), int(maxiter))
         if not self._h:
             raise OiError(self._lib.oi_last_error().decode())
         self._x = np.empty(6)
 
     def step(self):
         """None when finished, else the point (6,) whose f, g are needed."""
-        rc = self._lib.oi_cg_step(self._h, _ptr(self._x, ctypes.c_double))
+        rc = self._lib.oi_cg_step(self._h, _ptr(self._x))
         if rc < 0:
             _check(rc)
         return None if rc == 0 else self._x.copy()
 
     def feed(self, f, g):
-        g = np.ascontiguousarray(g, dtype=np.float64)
-        _check(self._lib.oi_cg_feed(self._h, float(f), _ptr(g, ctypes.c_double)))
+        g = _f64(g)
+        _check(self._lib.oi_cg_feed(self._h, float(f), _ptr(g)))
 
     def result(self):
         x = np.empty(6)
@@ -775,9 +627,9 @@ class CG:
         nfev = ctypes.c_int64()
         njev = ctypes.c_int64()
         nobj = ctypes.c_int64()
-        _check(self._lib.oi_cg_result(self._h, _ptr(x, ctypes.c_double), ctypes.byref(fun),
-                                      ctypes.byref(nit), ctypes.byref(st), ctypes.byref(nfev),
-                                      ctypes.byref(njev), ctypes.byref(nobj)))
+        _check(self._lib.oi_cg_result(self._h, _ptr(x), ctypes.byref(fun), ctypes.byref(nit),
+                                      ctypes.byref(st), ctypes.byref(nfev), ctypes.byref(njev),
+                                      ctypes.byref(nobj)))
         return dict(x=x, fun=fun.value, nit=nit.value, status=st.value, nfev=nfev.value,
                     njev=njev.value, nobj=nobj.value)
 
@@ -787,39 +639,28 @@ class CG:
             self._h = None
 
 
-def _dptr(t, ctype=ctypes.c_double):
-    """Device pointer of a torch tensor (plumbing for device_inputs=1 calls),
-    after checking what liboi assumes: a contiguous CUDA tensor whose element
-    type matches ``ctype`` (fp64 or int64, 8 bytes per element)."""
-    want = {ctypes.c_double: 'torch.float64', ctypes.c_int64: 'torch.int64'}[ctype]
-    if str(t.dtype) != want:
-        raise ValueError(f"device array must be {want}, got {t.dtype}")
-    if t.device.type != 'cuda':
-        raise ValueError(f"device array must be a CUDA tensor, got {t.device}")
-    if not t.is_contiguous():
-        raise ValueError("device arrays must be contiguous")
-    return ctypes.cast(t.data_ptr(), ctypes.POINTER(ctype))
-
-
 def smooth_fields(fields, vmax, mask, kern, **opt_kw):
     """oi_smooth_fields (GPR:65-76 for nf fields): fields [nf, ny, nx] host
     arrays; kern the Gaussian2DKernel array (odd square).  Returns [nf, ny, nx]."""
     lib = load()
-    f = np.ascontiguousarray(fields, dtype=np.float64)
+    f = _f64(fields)
     if f.ndim == 2:
         f = f[None]
     nf, ny, nx = f.shape
     vm = np.ascontiguousarray(np.broadcast_to(np.asarray(vmax, dtype=np.float64), (nf,)))
-    m = np.ascontiguousarray(mask, dtype=np.float64)
-    k = np.ascontiguousarray(kern, dtype=np.float64)
+    m = _f64(mask)
+    k = _f64(kern)
     if m.shape != (ny, nx) or k.ndim != 2 or k.shape[0] != k.shape[1] or k.shape[0] % 2 != 1:
         raise ValueError("mask must be [ny, nx] and kern an odd square")
     out = np.empty_like(f)
-    _check(lib.oi_smooth_fields(_ptr(f, ctypes.c_double), nf, ny, nx, _ptr(vm, ctypes.c_double),
-                                _ptr(m, ctypes.c_double), 0.0, _ptr(k, ctypes.c_double), k.shape[0],
-                                _ptr(out, ctypes.c_double), ctypes.byref(options(**opt_kw))))
+    _check(lib.oi_smooth_fields(_ptr(f), nf, ny, nx, _ptr(vm), _ptr(m), 0.0, _ptr(k), k.shape[0],
+                                _ptr(out), ctypes.byref(options(**opt_kw))))
     return out
 
+
+# The three day helpers below take device tensors on ANY GPU (_dptr with
+# device=None) and launch on ``device=`` (default 0): callers on other ranks
+# rely on that today, see DESIGN.md.
 
 def smooth_fields_device(fields_dev, vmax, mask_dev, kern, out_dev, **opt_kw):
     """oi_smooth_fields on HBM-resident tensors ([nf, ny, nx] fp64 in and out)."""
@@ -828,27 +669,27 @@ def smooth_fields_device(fields_dev, vmax, mask_dev, kern, out_dev, **opt_kw):
     if tuple(mask_dev.shape) != (ny, nx) or tuple(out_dev.shape) != (nf, ny, nx):
         raise ValueError("shape mismatch")
     vm = np.ascontiguousarray(np.broadcast_to(np.asarray(vmax, dtype=np.float64), (nf,)))
-    k = np.ascontiguousarray(kern, dtype=np.float64)
-    _check(lib.oi_smooth_fields(_dptr(fields_dev), nf, ny, nx, _ptr(vm, ctypes.c_double),
-                                _dptr(mask_dev), 0.0, _ptr(k, ctypes.c_double), k.shape[0],
-                                _dptr(out_dev), ctypes.byref(options(device_inputs=True, **opt_kw))))
+    k = _f64(kern)
+    _check(lib.oi_smooth_fields(_dptr(fields_dev, None), nf, ny, nx, _ptr(vm), _dptr(mask_dev, None),
+                                0.0, _ptr(k), k.shape[0], _dptr(out_dev, None),
+                                ctypes.byref(options(device_inputs=True, **opt_kw))))
     return out_dev
 
 
 def ball_query(pts, q, r, **opt_kw):
     """oi_ball_query on host arrays: returns (offs [Q+1], idx [offs[-1]])."""
     lib = load()
-    P = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 2)
-    Qa = np.ascontiguousarray(q, dtype=np.float64).reshape(-1, 2)
+    P = _f64(pts).reshape(-1, 2)
+    Qa = _f64(q).reshape(-1, 2)
     offs = np.zeros(len(Qa) + 1, dtype=np.int64)
     o = options(**opt_kw)
-    _check(lib.oi_ball_query(_ptr(P, ctypes.c_double), len(P), _ptr(Qa, ctypes.c_double), len(Qa),
-                             float(r), _ptr(offs, ctypes.c_int64), None, 0, ctypes.byref(o)))
+    _check(lib.oi_ball_query(_ptr(P), len(P), _ptr(Qa), len(Qa), float(r), _ptr(offs, ctypes.c_int64),
+                             None, 0, ctypes.byref(o)))
     idx = np.empty(int(offs[-1]), dtype=np.int64)
     if len(idx):
-        _check(lib.oi_ball_query(_ptr(P, ctypes.c_double), len(P), _ptr(Qa, ctypes.c_double),
-                                 len(Qa), float(r), _ptr(offs, ctypes.c_int64),
-                                 _ptr(idx, ctypes.c_int64), len(idx), ctypes.byref(o)))
+        _check(lib.oi_ball_query(_ptr(P), len(P), _ptr(Qa), len(Qa), float(r),
+                                 _ptr(offs, ctypes.c_int64), _ptr(idx, ctypes.c_int64), len(idx),
+                                 ctypes.byref(o)))
     return offs, idx
 
 
@@ -860,14 +701,14 @@ def ball_query_device(pts_dev, q_dev, r, counts_only=False, **opt_kw):
     M, Q = pts_dev.shape[0], q_dev.shape[0]
     offs = np.zeros(Q + 1, dtype=np.int64)
     o = options(device_inputs=True, **opt_kw)
-    _check(lib.oi_ball_query(_dptr(pts_dev), M, _dptr(q_dev), Q, float(r),
+    _check(lib.oi_ball_query(_dptr(pts_dev, None), M, _dptr(q_dev, None), Q, float(r),
                              _ptr(offs, ctypes.c_int64), None, 0, ctypes.byref(o)))
     if counts_only:
         return offs, None
     idx = torch.empty(int(offs[-1]), dtype=torch.int64, device=pts_dev.device)
     if idx.numel():
-        _check(lib.oi_ball_query(_dptr(pts_dev), M, _dptr(q_dev), Q, float(r),
-                                 _ptr(offs, ctypes.c_int64), _dptr(idx, ctypes.c_int64),
+        _check(lib.oi_ball_query(_dptr(pts_dev, None), M, _dptr(q_dev, None), Q, float(r),
+                                 _ptr(offs, ctypes.c_int64), _dptr(idx, None, ctypes.c_int64),
                                  idx.numel(), ctypes.byref(o)))
     return offs, idx
 
@@ -875,16 +716,15 @@ def ball_query_device(pts_dev, q_dev, r, counts_only=False, **opt_kw):
 def gather_rows(x_train, y_train, t_train, z, idx, **opt_kw):
     """oi_gather_rows on host arrays: returns (xyt [N, 3], z [N])."""
     lib = load()
-    cols = [np.ascontiguousarray(a, dtype=np.float64) for a in (x_train, y_train, t_train, z)]
+    cols = [_f64(a) for a in (x_train, y_train, t_train, z)]
     M = len(cols[0])
     if any(len(c) != M for c in cols):
         raise ValueError("training columns differ in length")
     I = np.ascontiguousarray(idx, dtype=np.int64)
     xyt = np.empty((len(I), 3))
     zo = np.empty(len(I))
-    _check(lib.oi_gather_rows(*[_ptr(c, ctypes.c_double) for c in cols], M, _ptr(I, ctypes.c_int64),
-                              len(I), _ptr(xyt, ctypes.c_double), _ptr(zo, ctypes.c_double),
-                              ctypes.byref(options(**opt_kw))))
+    _check(lib.oi_gather_rows(*[_ptr(c) for c in cols], M, _ptr(I, ctypes.c_int64), len(I), _ptr(xyt),
+                              _ptr(zo), ctypes.byref(options(**opt_kw))))
     return xyt, zo
 
 
@@ -898,8 +738,9 @@ def gather_rows_device(cols_dev, idx_dev, **opt_kw):
     xyt = torch.empty((N, 3), dtype=torch.float64, device=idx_dev.device)
     zo = torch.empty(N, dtype=torch.float64, device=idx_dev.device)
     if N:
-        _check(lib.oi_gather_rows(*[_dptr(c) for c in cols_dev], M, _dptr(idx_dev, ctypes.c_int64), N,
-                                  _dptr(xyt), _dptr(zo),
+        _check(lib.oi_gather_rows(*[_dptr(c, None) for c in cols_dev], M,
+                                  _dptr(idx_dev, None, ctypes.c_int64), N, _dptr(xyt, None),
+                                  _dptr(zo, None),
                                   ctypes.byref(options(device_inputs=True, **opt_kw))))
     return xyt, zo
 

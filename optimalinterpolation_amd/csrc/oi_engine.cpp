@@ -408,36 +408,6 @@ Context& context(int device, int64_t pool_bytes) {
   return *p;
 }
 
-// device buffer RAII
-struct DBuf {
-  void* p = nullptr;
-  size_t n = 0;
-  void reserve(size_t bytes) {
-    if (bytes <= n) return;
-    if (p) HC(hipFree(p));
-    p = nullptr;
-    HC(hipMalloc(&p, bytes));
-    n = bytes;
-  }
-  ~DBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-struct HBuf {  // pinned host
-  void* p = nullptr;
-  size_t n = 0;
-  void reserve(size_t bytes, unsigned flags = hipHostMallocDefault) {
-    if (bytes <= n) return;
-    if (p) HC(hipHostFree(p));
-    p = nullptr;
-    HC(hipHostMalloc(&p, bytes, flags));
-    n = bytes;
-  }
-  ~HBuf() {
-    if (p) (void)hipHostFree(p);
-  }
-};
-
 // ------------------------------------------------------------- the batch
 // One submitted ragged batch of cells ("ticket").  Host metadata is copied at
 // submission; host inputs are copied to the device at submission; outputs go
@@ -472,7 +442,7 @@ struct Job {
   int64_t id = 0;
   int64_t remaining = 0;
   size_t in_off = SIZE_MAX, in_bytes = 0;  // arena block holding the inputs' device copies
-  DBuf own;                                // fallback when the arena is full
+  DevBuf own;                              // fallback when the arena is full
   std::vector<double> r_host;              // staging for host inputs
 };
 
@@ -751,7 +721,7 @@ class Engine {
     if (jp->in_off != SIZE_MAX) ctx_.arena.release(jp->in_off, jp->in_bytes);
     jp->in_off = SIZE_MAX;
     auto it = jobs_.find(jp->id);
-    if (it != jobs_.end()) jobs_.erase(it);  // frees the job (its own DBuf, if any)
+    if (it != jobs_.end()) jobs_.erase(it);  // frees the job (its own DevBuf, if any)
   }
 
   void admit(Group& gr) {
@@ -1107,8 +1077,8 @@ class Engine {
   int cap_ = 1, G_ = 1, capG_ = 1;
   std::vector<Slot> slots_;
   std::vector<Group> groups_;
-  DBuf d_blk_, d_done_;
-  HBuf h_blk_, h_res_, h_flag_;
+  DevBuf d_blk_, d_done_;
+  HostBuf h_blk_, h_res_, h_flag_;
   size_t blk_ = 0;  // bytes of one group's round block
   double* hres_ = nullptr;  // result rows (host view)
   double* dres_ = nullptr;  // the same rows, device view
@@ -1124,19 +1094,12 @@ class Engine {
   std::chrono::steady_clock::time_point t_start_;
 };
 
-bool check_offs(const int64_t* offs, int64_t ncell) {
-  if (!offs || offs[0] != 0) return false;
-  for (int64_t c = 0; c < ncell; ++c)
-    if (offs[c + 1] < offs[c]) return false;
-  return true;
-}
-
 // Validates the oi_gpr_batch arguments and fills a Job (host metadata copied).
 int make_gpr_job(const double* xyt, const double* z, const int64_t* offs, int64_t ncell,
                  const double* xs, double mean, const double* x0, int32_t opt, const double* hyp,
                  double* out, int32_t* status, int32_t* info, const oi_options& o,
                  std::unique_ptr<Job>& job) {
-  if (ncell < 0 || !check_offs(offs, ncell)) return fail(OI_E_ARG, "bad offs / ncell");
+  if (int rc = oi_check_offs(offs, ncell, 0, "offs")) return rc;
   const int64_t N = ncell ? offs[ncell] : 0;
   if (ncell > 0 && ((N > 0 && (!xyt || !z)) || !xs || !out)) return fail(OI_E_ARG, "null input/output pointer");
   if (opt && !x0) return fail(OI_E_ARG, "opt=1 needs x0");
@@ -1200,7 +1163,7 @@ void oi_options_default(oi_options* o) {
 int oi_gpr_batch(const double* xyt, const double* z, const int64_t* offs, int64_t ncell,
                  const double* xs, double mean, const double* x0, int32_t opt, const double* hyp,
                  double* out, int32_t* status, int32_t* info, const oi_options* opts) {
-  if (ncell < 0 || !check_offs(offs, ncell)) return fail(OI_E_ARG, "bad offs / ncell");
+  if (int rc = oi_check_offs(offs, ncell, 0, "offs")) return rc;
   if (ncell == 0) return 0;
   const oi_options o = oi_resolve(opts);
   std::unique_ptr<Job> job;
@@ -1212,7 +1175,7 @@ int oi_gpr_batch(const double* xyt, const double* z, const int64_t* offs, int64_
 int oi_nlml_grad_batch(const double* xyt, const double* y, const double* mX, const int64_t* offs,
                        int64_t ncell, const double* h, double* nlz, double* grad, int32_t* status,
                        const oi_options* opts) {
-  if (ncell < 0 || !check_offs(offs, ncell)) return fail(OI_E_ARG, "bad offs / ncell");
+  if (int rc = oi_check_offs(offs, ncell, 0, "offs")) return rc;
   if (ncell == 0) return 0;
   const int64_t N = offs[ncell];
   if ((N > 0 && (!xyt || !y || !mX)) || !h || !nlz || !grad)

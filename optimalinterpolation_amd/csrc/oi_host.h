@@ -1,10 +1,12 @@
 // Host plumbing shared by every entry point of liboi.so: error reporting, the
-// exception-to-code ladder, option / device set-up, the RAII device buffer and
-// the per-stage event profiler.  Host code only; needs the HIP runtime, so the
+// exception-to-code ladder, option / device set-up, the ragged-offsets
+// validator, the RAII device / pinned buffers and owned stream, the workspace
+// chunk planner and the per-stage event profiler.  Host code only; needs the HIP runtime, so the
 // optimiser's files (cg.cpp, cg.hpp, cg_abi.cpp, task.hpp) do not include it.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <new>
 #include <string>
@@ -66,6 +68,21 @@ inline int oi_select_device(const oi_options& o) {
   return 0;
 }
 
+// The ragged offsets `name` of ncell >= 0 cells: non-null, starting at 0, every
+// cell with at least min_n rows (0: merely non-decreasing).  0 or OI_E_ARG.
+inline int oi_check_offs(const int64_t* offs, int64_t ncell, int64_t min_n, const char* name) {
+  const std::string s(name);
+  if (ncell < 0) return oi_set_last_error(OI_E_ARG, "negative ncell");
+  if (!offs) return oi_set_last_error(OI_E_ARG, ("null " + s).c_str());
+  if (offs[0] != 0) return oi_set_last_error(OI_E_ARG, (s + "[0] must be 0").c_str());
+  for (int64_t c = 0; c < ncell; ++c) {
+    const int64_t n = offs[c + 1] - offs[c];
+    if (n < 0) return oi_set_last_error(OI_E_ARG, (s + " must be non-decreasing").c_str());
+    if (n < min_n) return oi_set_last_error(OI_E_ARG, (s + ": every cell needs n >= 1").c_str());
+  }
+  return 0;
+}
+
 inline unsigned blocks(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
 inline int64_t up(int64_t v, int64_t q) { return (v + q - 1) / q * q; }
 
@@ -90,6 +107,13 @@ struct DevBuf {
     async = true;
     if (bytes) HC(hipMallocAsync(&p, bytes, s));
   }
+  void reserve(size_t bytes) {  // plain buffers: grow to at least `bytes`, contents dropped
+    if (bytes <= n) return;
+    if (p) HC(hipFree(p));
+    p = nullptr;
+    HC(hipMalloc(&p, bytes));
+    n = bytes;
+  }
   ~DevBuf() {
     if (p) (void)(async ? hipFreeAsync(p, st) : hipFree(p));
   }
@@ -97,7 +121,97 @@ struct DevBuf {
   T* as() const {
     return static_cast<T*>(p);
   }
+
+ private:
+  size_t n = 0;  // what reserve() holds
 };
+
+// Pinned host buffer.
+struct HostBuf {
+  void* p = nullptr;
+  HostBuf() = default;
+  HostBuf(const HostBuf&) = delete;
+  HostBuf& operator=(const HostBuf&) = delete;
+  void reserve(size_t bytes, unsigned flags = hipHostMallocDefault) {
+    if (bytes <= n) return;
+    if (p) HC(hipHostFree(p));
+    p = nullptr;
+    HC(hipHostMalloc(&p, bytes, flags));
+    n = bytes;
+  }
+  ~HostBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+  template <class T>
+  T* as() const {
+    return static_cast<T*>(p);
+  }
+
+ private:
+  size_t n = 0;
+};
+
+// A non-blocking stream of our own; destroyed (not synchronised) with its owner.
+struct OwnStream {
+  hipStream_t s = nullptr;
+  OwnStream() = default;
+  OwnStream(const OwnStream&) = delete;
+  OwnStream& operator=(const OwnStream&) = delete;
+  void create() { HC(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+  ~OwnStream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+};
+
+// Carves 256-byte-aligned arrays of doubles out of one workspace.
+struct Carver {
+  double* base;
+  int64_t off = 0;
+  double* take(int64_t doubles) {
+    double* p = base + off;
+    off += up(doubles, 32);
+    return p;
+  }
+};
+
+// The workspace budget in doubles: opts.pool_bytes, or 60 % of the free HBM.
+inline int64_t oi_workspace_budget(const oi_options& o) {
+  if (o.pool_bytes > 0) return o.pool_bytes / 8;
+  size_t fr = 0, tot = 0;
+  HC(hipMemGetInfo(&fr, &tot));
+  return (int64_t)((double)fr * 0.6) / 8;
+}
+
+// Chunks of consecutive cells whose workspace (cell_doubles(c) each, plus
+// `slack` per chunk) fits `budget` doubles, at most opts.max_pool (when set)
+// and `max_cells` cells each: chunk q is cells cuts[q] .. cuts[q + 1], and the
+// largest chunk needs `biggest` doubles.  `what` names the workspace in the
+// OI_E_NOMEM text of a cell that fits no chunk.
+struct ChunkPlan {
+  std::vector<int64_t> cuts;
+  int64_t biggest = 0;
+};
+template <class F>
+ChunkPlan plan_chunks(int64_t ncell, const oi_options& o, int64_t slack, int64_t max_cells, const char* what,
+                      F&& cell_doubles) {
+  const int64_t budget = oi_workspace_budget(o);
+  const int64_t cap = o.max_pool > 0 ? std::min<int64_t>(o.max_pool, max_cells) : max_cells;
+  ChunkPlan p;
+  p.cuts.push_back(0);
+  int64_t cur = slack;
+  for (int64_t c = 0; c < ncell; ++c) {
+    const int64_t d = cell_doubles(c);
+    if (slack + d > budget) throw NoMem{std::string("a cell's ") + what + " workspace does not fit pool_bytes"};
+    if (cur + d > budget || c - p.cuts.back() >= cap) {
+      p.cuts.push_back(c);
+      cur = slack;
+    }
+    cur += d;
+    p.biggest = std::max(p.biggest, cur);
+  }
+  p.cuts.push_back(ncell);
+  return p;
+}
 
 // opts.profile: HIP events around each stage on one stream, summed per stage
 // (names[kind]) into oi_profile_json with the stage's algorithmic flops / bytes.

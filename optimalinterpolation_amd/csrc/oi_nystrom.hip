@@ -363,11 +363,12 @@ struct Batch {
 int check_batch(Batch& b) {
   if (b.ncell < 0) return oi_set_last_error(OI_E_ARG, "negative ncell");
   if (b.ncell == 0) return 0;
-  if (!b.offs || !b.soffs || !b.sel || !b.xyt || !b.y) return oi_set_last_error(OI_E_ARG, "null pointer");
-  if (b.offs[0] != 0 || b.soffs[0] != 0) return oi_set_last_error(OI_E_ARG, "offs[0] must be 0");
+  if (!b.sel || !b.xyt || !b.y) return oi_set_last_error(OI_E_ARG, "null pointer");
+  if (int rc = oi_check_offs(b.offs, b.ncell, 1, "offs")) return rc;
+  if (int rc = oi_check_offs(b.soffs, b.ncell, 0, "soffs")) return rc;
   for (int64_t c = 0; c < b.ncell; ++c) {
     const int64_t n = b.offs[c + 1] - b.offs[c], M = b.soffs[c + 1] - b.soffs[c];
-    if (n < 1 || M < 1 || M > n) return oi_set_last_error(OI_E_ARG, "each cell needs 1 <= M <= n");
+    if (M < 1 || M > n) return oi_set_last_error(OI_E_ARG, "each cell needs 1 <= M <= n");
     for (int64_t k = b.soffs[c]; k < b.soffs[c + 1]; ++k)
       if (b.sel[k] < 0 || b.sel[k] >= n)
         return oi_set_last_error(OI_E_ARG, "inducing index out of range");
@@ -458,13 +459,15 @@ class Runner {
       : tab_(tab), nmax_(nmax), cap_(cap), st_((hipStream_t)o.stream), alloc_obj_(want_obj),
         alloc_pred_(want_pred) {
     if (own_stream) {
-      HC(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-      own_ = true;
+      own_.create();
+      st_ = own_.s;
     }
     res_.alloc(cap * NRES * 8);
     info_.alloc(cap * NINFO * sizeof(int32_t));
-    HC(hipHostMalloc((void**)&hr_, cap * NRES * 8, hipHostMallocDefault));
-    HC(hipHostMalloc((void**)&hi_, cap * NINFO * sizeof(int32_t), hipHostMallocDefault));
+    hres_.reserve(cap * NRES * 8);
+    hinfo_.reserve(cap * NINFO * sizeof(int32_t));
+    hr_ = hres_.as<double>();
+    hi_ = hinfo_.as<int32_t>();
     la_.bind(st_);
     sg_.on = o.profile != 0;
     sg_.st = st_;
@@ -515,11 +518,8 @@ class Runner {
     EW_.alloc(ch * ewd_ * 8);
     Dinv_.alloc(ch * nd64_ * 4096 * 8);
   }
-  ~Runner() {
-    if (own_ && st_) (void)hipStreamSynchronize(st_);
-    if (hr_) (void)hipHostFree(hr_);
-    if (hi_) (void)hipHostFree(hi_);
-    if (own_ && st_) (void)hipStreamDestroy(st_);
+  ~Runner() {  // the members (buffers first, the stream last) go after the stream's work
+    if (own_.s) (void)hipStreamSynchronize(own_.s);
   }
 
   // cells[k] at LINEAR hypers hyp[k*5 ..]; results into out[k]
@@ -867,6 +867,7 @@ class Runner {
 
   const std::vector<CellSrc>* tab_;
   int64_t nmax_ = 0, cap_ = 0;
+  OwnStream own_;  // declared before every buffer: destroyed after them
   hipStream_t st_;
   bool obj_ = false, pred_ = false, alloc_obj_, alloc_pred_;
   DevBuf res_, info_;
@@ -886,8 +887,8 @@ class Runner {
   std::vector<double> hypv_;
   int64_t ncq_ = 0;
   double mean_ = 0.0;
-  bool own_ = false;
-  double* hr_ = nullptr;       // pinned: the result copies stay asynchronous
+  HostBuf hres_, hinfo_;  // pinned: the result copies stay asynchronous
+  double* hr_ = nullptr;
   int32_t* hi_ = nullptr;
 };
 
@@ -1111,7 +1112,7 @@ struct oi_nystrom_session {
   // inputs of submitted batches are allocated, copied and freed on this stream
   // (stream-ordered): dropping a completed batch never drains the groups'
   // rounds in flight (a ticket's cells are in no round by then)
-  hipStream_t io = nullptr;
+  OwnStream io;
 
   ~oi_nystrom_session() {
     for (auto* p : cg)
@@ -1119,10 +1120,7 @@ struct oi_nystrom_session {
     grp.clear();
     pred.reset();
     tickets.clear();
-    if (io) {
-      (void)hipStreamSynchronize(io);
-      (void)hipStreamDestroy(io);
-    }
+    if (io.s) (void)hipStreamSynchronize(io.s);
   }
 
   void build_runners(int64_t nm, int64_t mm) {
@@ -1232,7 +1230,7 @@ extern "C" oi_nystrom_session* oi_nystrom_session_create(const oi_options* opts)
   if (oi_guarded([&] {
         s = std::make_unique<oi_nystrom_session>();
         s->o = o;
-        HC(hipStreamCreateWithFlags(&s->io, hipStreamNonBlocking));
+        s->io.create();
         return 0;
       }))
     return nullptr;
@@ -1264,7 +1262,7 @@ extern "C" int64_t oi_nystrom_session_submit(oi_nystrom_session* s, const double
     t->info = info;
     ticket = (int64_t)s->tickets.size();
     if (ncell > 0) {
-      t->dev.reset(new BatchDev(b, xs, s->o.device_inputs != 0, s->io));
+      t->dev.reset(new BatchDev(b, xs, s->o.device_inputs != 0, s->io.s));
       if (s->grp.empty() || b.nmax > s->nmax || b.mmax > s->mmax) {
         s->drain();  // no round in flight over the old Runners' workspaces
         s->build_runners(b.nmax, b.mmax);

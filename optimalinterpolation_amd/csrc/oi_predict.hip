@@ -252,16 +252,6 @@ int64_t cell_doubles(int64_t n, int64_t nt, bool cov, bool host_inputs) {
 constexpr int64_t CHUNK_SLACK = 8 * 32;  // rounding of the chunk-wide arrays (doubles)
 constexpr int64_t CHUNK_CELLS = 4096;    // cells per chunk at most (launch grids, descriptor arrays)
 
-struct Carver {
-  double* base;
-  int64_t off = 0;
-  double* take(int64_t doubles) {
-    double* p = base + off;
-    off += up(doubles, 32);
-    return p;
-  }
-};
-
 }  // namespace
 
 extern "C" int oi_gpr_predict_multi(const double* xyt, const double* z, const int64_t* offs,
@@ -269,14 +259,8 @@ extern "C" int oi_gpr_predict_multi(const double* xyt, const double* z, const in
                                     double mean, const double* hyp, double* fs, double* sd,
                                     double* lz, double* cov, int32_t* status,
                                     const oi_options* opts) {
-  if (ncell < 0) return oi_set_last_error(OI_E_ARG, "negative ncell");
-  if (!offs || !toffs) return oi_set_last_error(OI_E_ARG, "null offs / toffs");
-  if (offs[0] != 0) return oi_set_last_error(OI_E_ARG, "offs[0] must be 0");
-  if (toffs[0] != 0) return oi_set_last_error(OI_E_ARG, "toffs[0] must be 0");
-  for (int64_t c = 0; c < ncell; ++c) {
-    if (offs[c + 1] < offs[c]) return oi_set_last_error(OI_E_ARG, "offs must be non-decreasing");
-    if (toffs[c + 1] < toffs[c]) return oi_set_last_error(OI_E_ARG, "toffs must be non-decreasing");
-  }
+  if (int rc = oi_check_offs(offs, ncell, 0, "offs")) return rc;
+  if (int rc = oi_check_offs(toffs, ncell, 0, "toffs")) return rc;
   if (ncell == 0) return 0;
   const int64_t N = offs[ncell], T = toffs[ncell];
   if (!status) return oi_set_last_error(OI_E_ARG, "null status");
@@ -295,27 +279,9 @@ extern "C" int oi_gpr_predict_multi(const double* xyt, const double* z, const in
   return oi_guarded([&] {
     const bool host_in = o.device_inputs == 0, want_cov = cov != nullptr;
     hipStream_t st = (hipStream_t)o.stream;
-    // chunks: consecutive cells while their workspace fits the budget
-    int64_t budget = o.pool_bytes / 8;
-    if (o.pool_bytes <= 0) {
-      size_t fr = 0, tot = 0;
-      HC(hipMemGetInfo(&fr, &tot));
-      budget = (int64_t)((double)fr * 0.6) / 8;
-    }
-    const int64_t cap = o.max_pool > 0 ? std::min<int64_t>(o.max_pool, CHUNK_CELLS) : CHUNK_CELLS;
-    std::vector<int64_t> cuts{0};
-    int64_t cur = CHUNK_SLACK, biggest = 0;
-    for (int64_t c = 0; c < ncell; ++c) {
-      const int64_t d = cell_doubles(offs[c + 1] - offs[c], toffs[c + 1] - toffs[c], want_cov, host_in);
-      if (CHUNK_SLACK + d > budget) throw NoMem{"a cell's prediction workspace does not fit pool_bytes"};
-      if (cur + d > budget || c - cuts.back() >= cap) {
-        cuts.push_back(c);
-        cur = CHUNK_SLACK;
-      }
-      cur += d;
-      biggest = std::max(biggest, cur);
-    }
-    cuts.push_back(ncell);
+    const auto [cuts, biggest] = plan_chunks(ncell, o, CHUNK_SLACK, CHUNK_CELLS, "prediction", [&](int64_t c) {
+      return cell_doubles(offs[c + 1] - offs[c], toffs[c + 1] - toffs[c], want_cov, host_in);
+    });
     DevBuf ws((size_t)biggest * 8);
     oila::Stager la;
     la.bind(st);

@@ -591,19 +591,17 @@ extern "C" int oi_svgp_batch(const double* xyt, const double* y, const int64_t* 
                              double* elbo, int32_t* status, const oi_options* opts) {
   if (ncell < 0) return oi_set_last_error(OI_E_ARG, "negative ncell");
   if (ncell == 0) return 0;
-  if (!xyt || !y || !offs || !Z0 || !init || !xs || !pred || !status)
+  if (!xyt || !y || !Z0 || !init || !xs || !pred || !status)
     return oi_set_last_error(OI_E_ARG, "null pointer");
   if (M < 1 || M > MMAX) return oi_set_last_error(OI_E_ARG, "M must be in [1, 64]");
   if (batch < 1 || batch > BMAX) return oi_set_last_error(OI_E_ARG, "batch must be in [1, 256]");
   if (iterations < 0 || log_every < 0) return oi_set_last_error(OI_E_ARG, "negative count");
   if (!(lr > 0.0)) return oi_set_last_error(OI_E_ARG, "lr must be > 0");
-  if (offs[0] != 0) return oi_set_last_error(OI_E_ARG, "offs[0] must be 0");
-  for (int64_t c = 0; c < ncell; ++c) {
-    if (offs[c + 1] - offs[c] < 1) return oi_set_last_error(OI_E_ARG, "every cell needs n >= 1");
+  if (int rc = oi_check_offs(offs, ncell, 1, "offs")) return rc;
+  for (int64_t c = 0; c < ncell; ++c)
     for (int q = 0; q < 5; ++q)
       if (!(init[c * 6 + q] > (q == 4 ? 1e-6 : 0.0)))
         return oi_set_last_error(OI_E_ARG, "lengthscales / variances must be > 0 (noise > 1e-6)");
-  }
   const oi_options o = oi_resolve(opts);
   if (int rc = oi_select_device(o)) return rc;
   hipStream_t st = (hipStream_t)o.stream;
@@ -658,33 +656,24 @@ extern "C" int oi_svgp_batch(const double* xyt, const double* y, const int64_t* 
     nt = std::max(64, std::min(NT_MAX, nt / 64 * 64));
     auto* kern = nt < 256 ? k_svgp_train<true> : k_svgp_train<false>;
     HC(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (o.profile) {
-      HC(hipEventCreate(&ev0));
-      HC(hipEventCreate(&ev1));
-      HC(hipEventRecord(ev0, st));
-    }
+    // algorithmic flops per Adam step: the M x M x B products (A, S'A, S SA,
+    // Sbar, Kfbar, Lbar: 4.5 x 2 M^2 B) and M^3 terms (chol, inverse, adjoint:
+    // 5/3 x 2 M^3); logging passes are forward-only (~1/3 of a step)
+    const double dM = M, dB = batch;
+    const double fstep = 9.0 * dM * dM * dB + 10.0 / 3.0 * dM * dM * dM;
+    const double nsteps = iterations + (double)nlog / 3.0;
+    const char* const stage = "k_svgp_train";
+    StageTimer sg(&stage, 1);
+    sg.on = o.profile != 0;
+    sg.st = st;
+    sg.begin(0, fstep * nsteps * (double)ncell, 0.0);
     hipLaunchKernelGGL(kern, dim3((unsigned)ncell), dim3(nt), lb, st, dx, dy,
                        doffs.as<int64_t>(), sh, iterations, log_every, seed, lr, dth.as<double>(),
                        dmom.as<double>(), dg.as<double>(), dsc.as<double>(), dxs.as<double>(),
                        dpred.as<double>(), nlog ? delbo.as<double>() : nullptr, dst.as<int32_t>(),
                        panels, dtd.as<unsigned long long>());
-    HC(hipGetLastError());
-    if (o.profile) {
-      HC(hipEventRecord(ev1, st));
-      HC(hipEventSynchronize(ev1));
-      float ms = 0.f;
-      HC(hipEventElapsedTime(&ms, ev0, ev1));
-      (void)hipEventDestroy(ev0);
-      (void)hipEventDestroy(ev1);
-      // algorithmic flops per Adam step: the M x M x B products (A, S'A, S SA,
-      // Sbar, Kfbar, Lbar: 4.5 x 2 M^2 B) and M^3 terms (chol, inverse, adjoint:
-      // 5/3 x 2 M^3); logging passes are forward-only (~1/3 of a step)
-      const double dM = M, dB = batch;
-      const double fstep = 9.0 * dM * dM * dB + 10.0 / 3.0 * dM * dM * dM;
-      const double nsteps = iterations + (double)nlog / 3.0;
-      oi_profile_add("k_svgp_train", 1, ms, fstep * nsteps * (double)ncell, 0.0);
-    }
+    KCHK();
+    sg.end();
     if (timing) {
       unsigned long long t[16];
       HC(hipMemcpyAsync(t, dtd.p, sizeof(t), hipMemcpyDeviceToHost, st));
@@ -699,6 +688,7 @@ extern "C" int oi_svgp_batch(const double* xyt, const double* y, const int64_t* 
     if (elbo && nlog)
       HC(hipMemcpyAsync(elbo, delbo.p, (size_t)ncell * nlog * 8, hipMemcpyDeviceToHost, st));
     HC(hipStreamSynchronize(st));
+    sg.flush();
     return 0;
   });
 }

@@ -305,16 +305,6 @@ const char* kStage[S_COUNT] = {"svgp_model", "svgp_targets", "svgp_cov", "svgp_r
 constexpr int64_t CHUNK_CELLS = 32768;   // cells per chunk at most (the grids' y dimension)
 constexpr int64_t CHUNK_SLACK = 16 * 32;  // rounding of the chunk-wide arrays (doubles)
 
-struct Carver {
-  double* base;
-  int64_t off = 0;
-  double* take(int64_t doubles) {
-    double* p = base + off;
-    off += up(doubles, 32);
-    return p;
-  }
-};
-
 // What both entry points do.  pts / y / offs: the targets (y null) or the
 // observations of every cell; exactly one of (mean, var[, cov]) and elbo is set.
 struct Job {
@@ -350,27 +340,9 @@ int run(const Job& j, const oi_options& o) {
   HC(hipFuncSetAttribute((const void*)k_sp_model, hipFuncAttributeMaxDynamicSharedMemorySize, (int)model_lds(M)));
   HC(hipFuncSetAttribute((const void*)k_sp_targets, hipFuncAttributeMaxDynamicSharedMemorySize, (int)targets_lds(M)));
   HC(hipFuncSetAttribute((const void*)k_sp_cov, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cov_lds(M)));
-  int64_t budget = o.pool_bytes / 8;
-  if (o.pool_bytes <= 0) {
-    size_t fr = 0, tot = 0;
-    HC(hipMemGetInfo(&fr, &tot));
-    budget = (int64_t)((double)fr * 0.6) / 8;
-  }
-  // chunks: consecutive cells while their workspace fits the budget
-  const int64_t cap = o.max_pool > 0 ? std::min<int64_t>(o.max_pool, CHUNK_CELLS) : CHUNK_CELLS;
-  std::vector<int64_t> cuts{0};
-  int64_t cur = CHUNK_SLACK, biggest = 0;
-  for (int64_t c = 0; c < ncell; ++c) {
-    const int64_t d = cell_doubles(j, j.offs[c + 1] - j.offs[c], host_in);
-    if (CHUNK_SLACK + d > budget) throw NoMem{"a cell's SVGP prediction workspace does not fit pool_bytes"};
-    if (cur + d > budget || c - cuts.back() >= cap) {
-      cuts.push_back(c);
-      cur = CHUNK_SLACK;
-    }
-    cur += d;
-    biggest = std::max(biggest, cur);
-  }
-  cuts.push_back(ncell);
+  const auto [cuts, biggest] = plan_chunks(ncell, o, CHUNK_SLACK, CHUNK_CELLS, "SVGP prediction", [&](int64_t c) {
+    return cell_doubles(j, j.offs[c + 1] - j.offs[c], host_in);
+  });
   // per-cell prefix arrays: rows, covariance elements, ELBO partials
   std::vector<int64_t> pre(ncell + 1, 0);
   for (int64_t c = 0; c < ncell; ++c) {
@@ -470,11 +442,8 @@ extern "C" int oi_svgp_predict(const double* params, int32_t M, int64_t ncell, c
   if (ncell == 0) return 0;
   if (M < 1 || M > MMAX) return oi_set_last_error(OI_E_ARG, "M must be in [1, 64]");
   if (!params) return oi_set_last_error(OI_E_ARG, "null params");
-  if (!toffs) return oi_set_last_error(OI_E_ARG, "null toffs");
   if (!status) return oi_set_last_error(OI_E_ARG, "null status");
-  if (toffs[0] != 0) return oi_set_last_error(OI_E_ARG, "toffs[0] must be 0");
-  for (int64_t c = 0; c < ncell; ++c)
-    if (toffs[c + 1] < toffs[c]) return oi_set_last_error(OI_E_ARG, "toffs must be non-decreasing");
+  if (int rc = oi_check_offs(toffs, ncell, 0, "toffs")) return rc;
   if (toffs[ncell] > 0 && (!xs || !mean || !var)) return oi_set_last_error(OI_E_ARG, "null xs / mean / var");
   if (with_noise && cov)
     return oi_set_last_error(OI_E_ARG, "cov must be NULL with with_noise (no full-covariance predict_y)");
@@ -501,12 +470,9 @@ extern "C" int oi_svgp_elbo(const double* params, int32_t M, const double* xyt, 
   if (M < 1 || M > MMAX) return oi_set_last_error(OI_E_ARG, "M must be in [1, 64]");
   if (!params) return oi_set_last_error(OI_E_ARG, "null params");
   if (!xyt || !y) return oi_set_last_error(OI_E_ARG, "null xyt / y");
-  if (!offs) return oi_set_last_error(OI_E_ARG, "null offs");
   if (!elbo) return oi_set_last_error(OI_E_ARG, "null elbo");
   if (!status) return oi_set_last_error(OI_E_ARG, "null status");
-  if (offs[0] != 0) return oi_set_last_error(OI_E_ARG, "offs[0] must be 0");
-  for (int64_t c = 0; c < ncell; ++c)
-    if (offs[c + 1] - offs[c] < 1) return oi_set_last_error(OI_E_ARG, "offs: every cell needs n >= 1");
+  if (int rc = oi_check_offs(offs, ncell, 1, "offs")) return rc;
   const oi_options o = oi_resolve(opts);
   if (int rc = oi_select_device(o)) return rc;
   return oi_guarded([&] {

@@ -24,6 +24,42 @@ def test_header_matches_binding_list():
     assert declared() == sorted(_lib.EXPORTS)
 
 
+def _ctype(decl):
+    """The ctypes type of a C type as include/oi.h spells it."""
+    t = re.sub(r'\s+', ' ', re.sub(r'\bconst\b', '', decl)).strip().replace(' *', '*')
+    scalar = {'double': ctypes.c_double, 'int64_t': ctypes.c_int64, 'int32_t': ctypes.c_int32,
+              'uint64_t': ctypes.c_uint64, 'int': ctypes.c_int}
+    if t in scalar:
+        return scalar[t]
+    if t.endswith('*') and t[:-1] in scalar:
+        return ctypes.POINTER(scalar[t[:-1]])
+    if t in ('void', 'void*', 'char*'):
+        return {'void': None, 'void*': ctypes.c_void_p, 'char*': ctypes.c_char_p}[t]
+    if t == 'oi_options*':
+        return ctypes.POINTER(_lib.OiOptions)
+    assert re.fullmatch(r'(struct )?oi_\w+\*', t), f"unmapped C type {decl!r}"
+    return ctypes.c_void_p    # an opaque handle
+
+
+def test_binding_types_match_the_header():
+    """Every prototype of include/oi.h against _lib.SIGNATURES (which load()
+    applies), and struct oi_options against OiOptions, type by type."""
+    src = re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S))
+    protos = re.findall(r'([A-Za-z_][\w\s\*]*?)\b(oi_[a-z0-9_]+)\s*\(([^)]*)\)\s*;', src)
+    assert len(protos) == 32 and sorted(n for _, n, _ in protos) == sorted(_lib.SIGNATURES)
+    lib = _lib.load()
+    for ret, name, args in protos:
+        args = [a.strip() for a in args.split(',')] if args.strip() not in ('', 'void') else []
+        want = [_ctype(re.match(r'(.*?)\w+$', a).group(1)) for a in args]
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert (restype, list(argtypes)) == (_ctype(ret), want), name
+        fn = getattr(lib, name)
+        assert (fn.restype, list(fn.argtypes)) == (restype, list(argtypes)), name
+    body = re.search(r'struct\s+oi_options\s*\{(.*?)\}', src, flags=re.S).group(1)
+    fields = [(m.group(2), _ctype(m.group(1))) for m in re.finditer(r'([\w\s\*]+?)(\w+)\s*;', body)]
+    assert fields == list(_lib.OiOptions._fields_)
+
+
 def test_library_exports_every_symbol():
     lib = _lib.load()
     for name in declared():

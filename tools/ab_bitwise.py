@@ -8,7 +8,9 @@ must not change a single bit).  One small case per entry family:
                 in n and M
   prediction    gpr_predict_multi with the covariance, n and nt around the
                 64-tile, in one chunk and in several
-  SVGP          a short Adam run with logging
+  SVGP          a short Adam run with logging; predict_f with the covariance
+                and the ELBO at its parameters, in one chunk and in several
+  device inputs the Nystrom fit and the SVGP run again on device tensors
   day helpers   smooth_fields, ball query + gather
   profile       stage names and launch counts of the two staged paths; the main
                 engine's kernels with their launch counts and counted flops
@@ -54,6 +56,11 @@ def _stages(_lib, prefix):
     return np.array(names), np.array([k[n]['launches'] for n in names], dtype=np.int64)
 
 
+def _cuda(*arrays):
+    import torch
+    return [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays]
+
+
 def _nystrom(_lib, synthetic):
     from optimalinterpolation_amd import nystrom
     ns, Ms = [70, 130, 200, 260], np.array([20, 33, 64, 65])
@@ -68,6 +75,8 @@ def _nystrom(_lib, synthetic):
     names, launches = _stages(_lib, 'nys_')
     x0 = nystrom.default_x0()
     fit, fst, finfo = _lib.nystrom_fit_batch(c.xyt, y, c.offs, sel, soffs, x0, c.xs, c.mean, maxiter=100)
+    dfit = _lib.nystrom_fit_batch(*_cuda(c.xyt, y), c.offs, sel, soffs, x0, c.xs, c.mean, maxiter=100,
+                                  device_inputs=True)
     with _lib.NystromSession(maxiter=100) as s:
         t = []
         for a, b in [(0, 2), (2, 4)]:
@@ -78,7 +87,8 @@ def _nystrom(_lib, synthetic):
     return dict(nys_nlz=nlz, nys_grad=grad, nys_pred=pred, nys_st=st, nys_stage_names=names,
                 nys_stage_launches=launches, nys_fit=fit, nys_fit_st=fst, nys_fit_info=finfo,
                 nys_ses=np.concatenate([r[0] for r in res]), nys_ses_st=np.concatenate([r[1] for r in res]),
-                nys_ses_info=np.concatenate([r[2] for r in res]))
+                nys_ses_info=np.concatenate([r[2] for r in res]),
+                nys_dev_fit=dfit[0], nys_dev_fit_st=dfit[1], nys_dev_fit_info=dfit[2])
 
 
 def _predict(_lib, synthetic):
@@ -110,9 +120,29 @@ def _svgp(_lib):
     Z = np.stack([x[k * n:k * n + M] for k in range(nc)])
     init = np.tile([25e3, 25e3, 1.0, 1.0, 0.1, 0.3], (nc, 1))
     xs = np.tile([1e4, -2e4, 4.0], (nc, 1))
-    pred, st, params, elbo = _lib.svgp_batch(x, y, [0, n, 2 * n], Z, init, xs, batch=16, iterations=50,
-                                             log_every=10, seed=3, want_params=True)
-    return dict(svgp_pred=pred, svgp_st=st, svgp_params=params, svgp_elbo=elbo)
+    kw = dict(batch=16, iterations=50, log_every=10, seed=3, want_params=True)
+    offs = [0, n, 2 * n]
+    pred, st, params, elbo = _lib.svgp_batch(x, y, offs, Z, init, xs, **kw)
+    dev = _lib.svgp_batch(*_cuda(x, y), offs, Z, init, xs, device_inputs=True, **kw)
+    r = dict(svgp_pred=pred, svgp_st=st, svgp_params=params, svgp_elbo=elbo, svgp_dev_pred=dev[0],
+             svgp_dev_st=dev[1], svgp_dev_params=dev[2], svgp_dev_elbo=dev[3])
+    _lib.profile_reset()
+    _lib.svgp_batch(x, y, offs, Z, init, xs, profile=True, **kw)
+    k = _lib.profile_json()['kernels']['k_svgp_train']
+    r.update(svgp_train_launches=np.array([k['launches']]), svgp_train_flops=np.array([k['flops']]))
+    # predict_f with the covariance at 3 and 70 targets, and the ELBO: one chunk, then one cell per chunk
+    toffs = [0, 3, 73]
+    ts = x[:73] + rng.normal(0, 1.0, (73, 3)) * [5e3, 5e3, 0.5]
+    for tag, ckw in (('', {}), ('_chunked', dict(max_pool=1))):
+        _lib.profile_reset()
+        mean, var, cov, pst = _lib.svgp_predict(params, ts, toffs, cov=True, profile=True, **ckw)
+        el, est = _lib.svgp_elbo(params, x, y, offs, profile=True, **ckw)
+        names, launches = _stages(_lib, 'svgp_')
+        r.update({f'svgp_pf_mean{tag}': mean, f'svgp_pf_var{tag}': var, f'svgp_pf_cov{tag}': cov,
+                  f'svgp_pf_st{tag}': pst, f'svgp_full_elbo{tag}': el, f'svgp_full_elbo_st{tag}': est,
+                  f'svgp_stage_names{tag}': names, f'svgp_stage_launches{tag}': launches})
+    assert r['svgp_stage_launches_chunked'].max() > r['svgp_stage_launches'].max(), "max_pool=1 made no second chunk"
+    return r
 
 
 def _day(_lib):
