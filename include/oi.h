@@ -208,6 +208,10 @@ int oi_nystrom_batch(const double* xyt, const double* y, const int64_t* offs, in
                      const double* xs, double mean, double* nlz, double* grad, double* pred,
                      int32_t* status, const oi_options* opts);
 
+/* The Nystrom prediction at many targets per cell with the posterior
+ * covariance -- NB1 GPR(approx=True) with xs of size ns x 3 -- is declared in
+ * its own header, include/oi_nystrom_multi.h. */
+
 /* NB1 code cell 5 for a ragged batch: minimize(SMLII, x0, args=(x, y, True, M),
  * method='CG', jac=True) per cell (the restated scipy CG, maxiter <0 => 1000 =
  * len(x0)*200; gtol from opts), then GPR(approx=True, returnprior=True) at the

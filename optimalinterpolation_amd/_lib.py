@@ -89,6 +89,16 @@ def _signatures():
 SIGNATURES = _signatures()
 EXPORTS = tuple(SIGNATURES)
 
+# the same for include/oi_nystrom_multi.h, the header of the one entry point
+# that include/oi.h does not declare (tests/test_nystrom_predict_multi_abi.py
+# compares the two type by type)
+SIGNATURES_NYSTROM_MULTI = {
+    'oi_nystrom_predict_multi': (ctypes.c_int, [c_double_p, c_double_p, c_int64_p, ctypes.c_int64, c_int64_p,
+                                                c_int64_p, c_double_p, c_double_p, c_int64_p, ctypes.c_double,
+                                                c_double_p, c_double_p, c_double_p, c_int32_p,
+                                                ctypes.POINTER(OiOptions)]),
+}
+
 
 def load():
     """Load liboi.so (once).  Raises OiError when it has not been built."""
@@ -99,7 +109,7 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise OiError(f"{LIB_PATH} not built: run `make -C {_HERE}` (or __graft_entry__.build())")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in SIGNATURES.items():
+        for name, (restype, argtypes) in {**SIGNATURES, **SIGNATURES_NYSTROM_MULTI}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -446,6 +456,42 @@ def nystrom_batch(xyt, y, offs, sel, soffs, hyp, xs=None, mean=0.0, objective=Tr
                                 _ptr(nlz), _ptr(grad), _ptr(pred), _ptr(status, ctypes.c_int32),
                                 ctypes.byref(o)))
     return nlz, grad, pred, status
+
+
+def nystrom_predict_multi(xyt, y, offs, sel, soffs, hyp, xs, toffs, mean=0.0, cov=False, **opt_kw):
+    """oi_nystrom_predict_multi: the Nystrom prediction of every cell at its own
+    list of targets (``xs`` [T x 3], cell c owning rows toffs[c]:toffs[c+1]) at
+    LINEAR hypers ``hyp`` [ncell x 5]; ``sel``/``soffs`` as nystrom_batch.
+    Returns (fs [T], sd [T], cov | None, status [ncell]); ``cov`` is the flat
+    array of the cells' nt x nt matrices back to back (``split_cov``).  With
+    device_inputs=True ``xyt`` / ``y`` are fp64 contiguous torch tensors on
+    cuda:``device``; targets, offsets and hypers stay on the host."""
+    offs, toffs = _i64(offs), _i64(toffs)
+    xs = _f64(xs).reshape(-1, 3)
+    ncell = len(offs) - 1
+    if len(toffs) != ncell + 1 or toffs[0] != 0 or toffs[-1] != xs.shape[0]:
+        raise ValueError("inconsistent ragged batch")
+    hyp = _f64(hyp).reshape(-1, 5)
+    if hyp.shape[0] != ncell:
+        raise ValueError("hyp must be [ncell x 5]")
+    dev_in, dev = bool(opt_kw.get('device_inputs')), int(opt_kw.get('device', 0))
+    px, py, _keep = _obs(xyt, y, offs, dev_in, dev)
+    if dev_in:
+        _sync_producers(dev)
+    sel, soffs = _inducing(sel, soffs, ncell, "inconsistent ragged batch")
+    T = int(toffs[-1])
+    fs = np.empty(T)
+    sd = np.empty(T)
+    nt = np.diff(toffs)
+    cova = np.empty(int((nt * nt).sum())) if cov else None
+    status = np.zeros(ncell, dtype=np.int32)
+    o = options(**opt_kw)
+    _check(load().oi_nystrom_predict_multi(px, py, _ptr(offs, ctypes.c_int64), ncell,
+                                           _ptr(sel, ctypes.c_int64), _ptr(soffs, ctypes.c_int64),
+                                           _ptr(hyp), _ptr(xs), _ptr(toffs, ctypes.c_int64), float(mean),
+                                           _ptr(fs), _ptr(sd), _ptr(cova), _ptr(status, ctypes.c_int32),
+                                           ctypes.byref(o)))
+    return fs, sd, cova, status
 
 
 def _nystrom_fit_args(xyt, y, offs, sel, soffs, x0, xs, device_inputs, device):

@@ -26,6 +26,9 @@
 //   dnlZ_d = sum((Ki - A A') * dK_d)/2, dnlZ_3 = sum(Q * 2K)/2, dnlZ_4 = sn2 tr(Q)
 //   (exact K, dK: NB1 SMLII quirks kept)
 //   predict: fs = mean + k*.A;  sd = sqrt(sf2 - k*'Ki k*);  prior sd = sqrt(sf2)
+//   predict at nt targets (oi_nystrom_predict_multi): after the same set-up,
+//   cov = Kxs - (Kxsx'Kxsx/sn2 - V'V), V = W Kxsx, by one fused MFMA kernel per
+//   cell (k_nys_cov_mfma); the nt x nt err is never formed
 //
 // Every dense step -- the eigendecomposition, the Cholesky, the products --
 // is a hand-written gfx950 kernel of oi_linalg.hip (no LAPACK / rocSOLVER /
@@ -46,6 +49,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/oi_nystrom_multi.h"
 #include "oi_gemm.h"
 #include "oi_host.h"
 #include "oi_linalg.h"
@@ -328,17 +332,111 @@ __global__ void __launch_bounds__(256) k_nys_grad_mfma(const double* __restrict_
     for (int q = 0; q < 5; ++q) part[(size_t)tile * 5 + q] = v[q];
 }
 
+// ---- prediction at many targets per cell (oi_nystrom_predict_multi) ----
+// NB1 GPR(approx=True) with xs of size nt x 3:
+//   Kxsx = SGPkernel(x, xs=xs) (n x nt), Kxs = SGPkernel(xs) (nt x nt)
+//   err = Kxsx' Ki Kxsx = Kxsx'Kxsx / sn2 - V'V,  V = W Kxsx (M x nt)
+//   fs = mean + Kxsx' A,  cov = Kxs - err,  sd = sqrt(diag(cov))
+
+// out[a + nt k] = sf2 (1 + Q) exp(-Q), Q = |sc[k] - ts[a]|: Kxsx' (nt x n,
+// column-major), from the scaled observations sc and scaled targets ts
+__global__ void k_nys_cross_t(const double* __restrict__ ts, int64_t nt,
+                              const double* __restrict__ sc, int64_t n, double sf2,
+                              double* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= nt * n) return;
+  const int64_t a = e % nt, k = e / nt;
+  const double* o = sc + k * 3;
+  const double* b = ts + a * 3;
+  out[e] = matern32(sf2, o[0] - b[0], o[1] - b[1], o[2] - b[2]);
+}
+
+// fs[a] = mean + sum_k KxT[a + nt k] A[k]  (one 256-thread block per target:
+// the order of k_nys_dot, the same for every target of every call)
+__global__ void __launch_bounds__(256) k_nys_fs(const double* __restrict__ KxT, int64_t nt,
+                                                int64_t n, const double* __restrict__ A,
+                                                double mean, double* __restrict__ fs) {
+  __shared__ double red[4];
+  const int64_t a = blockIdx.x;
+  double v[1] = {0.0};
+  for (int64_t i = threadIdx.x; i < n; i += 256) v[0] += KxT[a + nt * i] * A[i];
+  block_sum<1>(v, red);
+  if (threadIdx.x == 0) fs[a] = mean + v[0];
+}
+
+// The posterior covariance without err as a matrix: per lower 64 x 64 tile
+// (i >= j) of the nt x nt output the MFMA core accumulates
+//   acc1 = (Kxsx'Kxsx)_ij over the n rows   (Kp: k_nys_pack of Kxsx', nch1 chunks of 16)
+//   acc2 = (V'V)_ij       over the M rows   (Vp: k_nys_pack of V',    nch2 chunks of 16)
+// and the epilogue forms cov(a, b) = Kxs(a, b) - (acc1 / sn2 - acc2), Kxs
+// regenerated from the scaled targets (diagonal sf2 exactly), stores it at
+// (a, b) and (b, a) of the row-major nt x nt output -- in a diagonal tile from
+// the entries with a >= b -- and the diagonal into var.  cov may be null: the
+// grid is then the Tt diagonal tiles (blockIdx.x = i = j) and only var is
+// written, by the same arithmetic.
+__global__ void __launch_bounds__(256) k_nys_cov_mfma(const double* __restrict__ Kp, int nch1,
+                                                      const double* __restrict__ Vp, int nch2,
+                                                      int Tt, const double* __restrict__ ts,
+                                                      int64_t nt, double sf2, double sn2,
+                                                      double* __restrict__ cov,
+                                                      double* __restrict__ var) {
+  __shared__ __attribute__((aligned(16))) double lds[GEMM1_LDS];
+  int i = blockIdx.x, j = blockIdx.x;
+  if (cov) {
+    const int tile = blockIdx.x;
+    i = (int)((sqrt(8.0 * tile + 1.0) - 1.0) * 0.5);
+    while ((i + 1) * (i + 2) / 2 <= tile) ++i;
+    while (i * (i + 1) / 2 > tile) --i;
+    j = tile - i * (i + 1) / 2;
+  }
+  Quad acc1, acc2;
+  quad_zero(acc1);
+  quad_zero(acc2);
+  gemm1_kmajor<false>(acc1, lds, nch1, 0u, [=](int p, const double*& a, const double*& b) {
+    a = Kp + ((size_t)p * Tt + i) * 4096;
+    b = Kp + ((size_t)p * Tt + j) * 4096;
+  });
+  gemm1_kmajor<false>(acc2, lds, nch2, 0u, [=](int p, const double*& a, const double*& b) {
+    a = Vp + ((size_t)p * Tt + i) * 4096;
+    b = Vp + ((size_t)p * Tt + j) * 4096;
+  });
+  double* cs = lds;  // [3][128] scaled targets, rows i | columns j
+  const int t = threadIdx.x;
+  if (t < 128) {
+    const int64_t a = t < 64 ? (int64_t)i * 64 + t : (int64_t)j * 64 + (t - 64);
+    for (int d = 0; d < 3; ++d) cs[d * 128 + t] = a < nt ? ts[3 * a + d] : 0.0;
+  }
+  __syncthreads();
+  for (int mb = 0; mb < 2; ++mb)
+    for (int nb = 0; nb < 2; ++nb)
+      for (int r = 0; r < 4; ++r) {
+        const int m = acc1_row(mb, r), nn = acc1_col(nb);
+        const int64_t a = (int64_t)i * 64 + m, b = (int64_t)j * 64 + nn;
+        if (a >= nt || b >= nt || (i == j && m < nn)) continue;
+        const double err = acc1.c[mb][nb][r] / sn2 - acc2.c[mb][nb][r];
+        const double kxs = a == b ? sf2
+                                  : matern32(sf2, cs[m] - cs[64 + nn], cs[128 + m] - cs[128 + 64 + nn],
+                                             cs[256 + m] - cs[256 + 64 + nn]);
+        const double c = kxs - err;
+        if (cov) {
+          cov[(size_t)a * nt + b] = c;
+          if (a != b) cov[(size_t)b * nt + a] = c;
+        }
+        if (a == b) var[a] = c;
+      }
+}
+
 // ------------------------------------------------------------------- host --
 
 // opts.profile: HIP events around each stage of each cell, summed per stage
 // into oi_profile_json (algorithmic flops / bytes per stage alongside)
 enum { S_BUILD, S_EIGH, S_EIGH_VEC, S_EIGH_ORTH, S_EIGH_BACK, S_PANEL, S_KI, S_APPLY, S_LOGDET, S_GRAD,
-       S_PRED, S_COUNT };
+       S_PRED, S_PREDM, S_COUNT };
 // nys_eigh = the Householder tridiagonalisation; the eigensolver's other phases
 // are timed as their own stages
 const char* kStage[S_COUNT] = {"nys_build",  "nys_eigh",   "nys_eigh_vectors", "nys_eigh_orth",
                                "nys_eigh_back", "nys_panels", "nys_ki_gemm", "nys_apply",
-                               "nys_logdet", "nys_grad",   "nys_predict"};
+                               "nys_logdet", "nys_grad",   "nys_predict", "nys_predict_multi"};
 // per-cell device results: [r.A, sum log diag(L) + sum log st / 2, g0..g4 raw
 // sums, k*.A, |k*|^2, |W k*|^2]
 constexpr int NRES = 10;
@@ -426,6 +524,25 @@ struct BatchDev {
       rows[c] = CellSrc{dx + b.offs[c] * 3, dy + b.offs[c], dsel.as<int64_t>() + b.soffs[c],
                         xs ? dxs.as<double>() + c * 3 : nullptr, b.offs[c + 1] - b.offs[c],
                         b.soffs[c + 1] - b.soffs[c]};
+  }
+};
+
+// Many-target prediction of one call (oi_nystrom_predict_multi): the targets
+// and outputs of every cell on the device, and the scratch of one cell (sized
+// for the call's largest, reused from cell to cell in stream order).
+struct MultiDev {
+  const double* xs = nullptr;      // [T x 3] targets (device)
+  const int64_t* toffs = nullptr;  // [ncell + 1] (host): cell c owns rows toffs[c] .. toffs[c+1]-1
+  const int64_t* coffs = nullptr;  // [ncell + 1] (host): cell c's covariance starts at coffs[c]
+  double* fs = nullptr;            // [T]
+  double* var = nullptr;           // [T] diag(Kxs - err)
+  double* cov = nullptr;           // [coffs[ncell]] or null
+  double *ts = nullptr, *KxT = nullptr, *VT = nullptr, *Kp = nullptr, *Vp = nullptr;
+  // doubles of one cell's scratch: scaled targets, Kxsx' (nt x n), V' (nt x M)
+  // and their zero-padded k-major tiles
+  static int64_t cell_doubles(int64_t n, int64_t M, int64_t nt) {
+    const int64_t Tt = (nt + 63) / 64;
+    return up(3 * nt, 32) + up(nt * n, 32) + up(nt * M, 32) + ((n + 63) / 64 + (M + 63) / 64) * Tt * 4096;
   }
 };
 
@@ -521,6 +638,10 @@ class Runner {
   ~Runner() {  // the members (buffers first, the stream last) go after the stream's work
     if (own_.s) (void)hipStreamSynchronize(own_.s);
   }
+
+  // every later evaluation also predicts cell id c at its targets m->toffs[c] ..
+  // (fs, var, cov of *m, which must outlive those evaluations)
+  void set_multi(const MultiDev* m) { multi_ = m; }
 
   // cells[k] at LINEAR hypers hyp[k*5 ..]; results into out[k]
   void run(const std::vector<int64_t>& cells, const double* hyp, double mean, CellOut* out,
@@ -863,6 +984,41 @@ class Runner {
       KCHK();
       sg.end();
     }
+    if (multi_) predict_multi(R, Wt, Av);
+  }
+
+  // the cell's nt targets: Kxsx' (nt x n), fs, V' = Kxsx' W' (nt x M), then the
+  // fused covariance kernel on the packed operands (k_nys_cov_mfma)
+  void predict_multi(const CellRefs& R, const double* Wt, const double* Av) {
+    const MultiDev& m = *multi_;
+    const int64_t t0 = m.toffs[R.c], nt = m.toffs[R.c + 1] - t0;
+    if (nt == 0) return;
+    hipStream_t st = st_;
+    const double dn = R.dn, dM = R.dM, dt = (double)nt;
+    const int Tt = (int)blocks(nt, 64), Tkn = (int)blocks(R.n, 64), Tkm = (int)blocks(R.M, 64);
+    sg_.begin(S_PREDM, 2.0 * dt * dn * dM + dt * dt * (dn + dM) + 2.0 * dt * dn,
+              8.0 * (2.0 * dt * dn + 2.0 * dt * dM + dn * dM + (m.cov ? dt * dt : dt)));
+    hipLaunchKernelGGL(k_nys_scale, dim3(blocks(nt, 256)), dim3(256), 0, st, m.xs + t0 * 3, nt, R.hp[0],
+                       R.hp[1], R.hp[2], m.ts, nullptr);
+    KCHK();
+    hipLaunchKernelGGL(k_nys_cross_t, dim3(blocks(nt * R.n, 256)), dim3(256), 0, st, m.ts, nt, R.sc, R.n,
+                       R.hp[3], m.KxT);
+    KCHK();
+    hipLaunchKernelGGL(k_nys_fs, dim3((unsigned)nt), dim3(256), 0, st, m.KxT, nt, R.n, Av, mean_,
+                       m.fs + t0);
+    KCHK();
+    oila::gemm(la_, st, false, false,
+               {oila::Gemm{m.KxT, Wt, m.VT, (int)nt, R.iM, R.in, (int)nt, R.in, (int)nt, 1.0, 0.0, 0}});  // V' = Kxsx' W'
+    hipLaunchKernelGGL(k_nys_pack, dim3((unsigned)(Tt * Tkn)), dim3(256), 0, st, m.KxT, nt, R.n, Tt, m.Kp);
+    KCHK();
+    hipLaunchKernelGGL(k_nys_pack, dim3((unsigned)(Tt * Tkm)), dim3(256), 0, st, m.VT, nt, R.M, Tt, m.Vp);
+    KCHK();
+    double* cov = m.cov ? m.cov + m.coffs[R.c] : nullptr;
+    hipLaunchKernelGGL(k_nys_cov_mfma, dim3((unsigned)(cov ? Tt * (Tt + 1) / 2 : Tt)), dim3(256), 0, st,
+                       m.Kp, (int)blocks(R.n, 16), m.Vp, (int)blocks(R.M, 16), Tt, m.ts, nt, R.hp[3],
+                       R.hp[4], cov, m.var + t0);
+    KCHK();
+    sg_.end();
   }
 
   const std::vector<CellSrc>* tab_;
@@ -887,6 +1043,7 @@ class Runner {
   std::vector<double> hypv_;
   int64_t ncq_ = 0;
   double mean_ = 0.0;
+  const MultiDev* multi_ = nullptr;
   HostBuf hres_, hinfo_;  // pinned: the result copies stay asynchronous
   double* hr_ = nullptr;
   int32_t* hi_ = nullptr;
@@ -979,6 +1136,99 @@ extern "C" int oi_nystrom_batch(const double* xyt, const double* y, const int64_
         pred[c * 3 + 1] = out[c].sd;
         pred[c * 3 + 2] = out[c].sprior;
       }
+    }
+    return 0;
+  });
+}
+
+extern "C" int oi_nystrom_predict_multi(const double* xyt, const double* y, const int64_t* offs,
+                                        int64_t ncell, const int64_t* sel, const int64_t* soffs,
+                                        const double* hyp, const double* xs, const int64_t* toffs,
+                                        double mean, double* fs, double* sd, double* cov,
+                                        int32_t* status, const oi_options* opts) {
+  Batch b{xyt, y, offs, ncell, sel, soffs};
+  if (int rc = check_batch(b)) return rc;
+  if (ncell == 0) return 0;
+  if (int rc = oi_check_offs(toffs, ncell, 0, "toffs")) return rc;
+  if (!hyp) return oi_set_last_error(OI_E_ARG, "null hyp");
+  if (!status) return oi_set_last_error(OI_E_ARG, "null status");
+  const int64_t T = toffs[ncell];
+  if (T > 0 && (!xs || !fs || !sd)) return oi_set_last_error(OI_E_ARG, "null xs / fs / sd");
+  for (int64_t q = 0; q < ncell * 5; ++q)
+    if (!(hyp[q] > 0.0)) return oi_set_last_error(OI_E_ARG, "hypers must be > 0");
+  // oila's operands take 32-bit byte offsets: Kxsx and cov stay below 2 GiB each
+  constexpr int64_t LIM = 0x7FFFFFF0 / 8;
+  std::vector<int64_t> coffs(ncell + 1, 0);
+  for (int64_t c = 0; c < ncell; ++c) {
+    const int64_t n = offs[c + 1] - offs[c], nt = toffs[c + 1] - toffs[c];
+    if (nt * n >= LIM || nt * nt >= LIM)
+      return oi_set_last_error(OI_E_ARG, "cell too large (Kxsx or cov reaches 2 GiB)");
+    coffs[c + 1] = coffs[c] + nt * nt;
+  }
+  const oi_options o = oi_resolve(opts);
+  if (int rc = oi_select_device(o)) return rc;
+  return oi_guarded([&] {
+    hipStream_t st = (hipStream_t)o.stream;
+    const bool want_cov = cov != nullptr;
+    // one cell's scratch (n x nt, M x nt and their tiles), the call's targets and outputs
+    const int64_t budget = oi_workspace_budget(o);
+    int64_t tsd = 0, kxd = 0, vtd = 0, kpd = 0, vpd = 0;  // each scratch array at its largest
+    for (int64_t c = 0; c < ncell; ++c) {
+      const int64_t n = offs[c + 1] - offs[c], M = soffs[c + 1] - soffs[c], nt = toffs[c + 1] - toffs[c];
+      const int64_t Tt = (nt + 63) / 64;
+      if (MultiDev::cell_doubles(n, M, nt) + (want_cov ? nt * nt : 0) > budget)
+        throw NoMem{"a cell's Nystrom prediction workspace does not fit pool_bytes"};
+      tsd = std::max(tsd, 3 * nt);
+      kxd = std::max(kxd, nt * n);
+      vtd = std::max(vtd, nt * M);
+      kpd = std::max(kpd, (n + 63) / 64 * Tt * 4096);
+      vpd = std::max(vpd, (M + 63) / 64 * Tt * 4096);
+    }
+    const int64_t total = up(tsd, 32) + up(kxd, 32) + up(vtd, 32) + kpd + vpd + up(3 * T, 32) +
+                          2 * up(T, 32) + (want_cov ? up(coffs[ncell], 32) : 0);
+    if (total > budget)
+      throw NoMem{"the call's targets and covariances do not fit pool_bytes: pass fewer cells per call"};
+    DevBuf ws((size_t)total * 8);
+    Carver cv{static_cast<double*>(ws.p)};
+    double* dxs = cv.take(3 * T);
+    MultiDev md;
+    md.xs = dxs;
+    md.toffs = toffs;
+    md.coffs = coffs.data();
+    md.fs = cv.take(T);
+    md.var = cv.take(T);
+    md.cov = want_cov ? cv.take(coffs[ncell]) : nullptr;
+    md.ts = cv.take(tsd);
+    md.KxT = cv.take(kxd);
+    md.VT = cv.take(vtd);
+    md.Kp = cv.take(kpd);
+    md.Vp = cv.take(vpd);
+    BatchDev bd(b, nullptr, o.device_inputs != 0, st);
+    if (T > 0) HC(hipMemcpyAsync(dxs, xs, T * 3 * 8, hipMemcpyHostToDevice, st));
+    std::vector<CellOut> out(ncell);
+    {
+      Runner R(&bd.rows, b.nmax, b.mmax, ncell, o, false, false);
+      R.set_multi(&md);
+      std::vector<int64_t> cells(ncell);
+      for (int64_t c = 0; c < ncell; ++c) cells[c] = c;
+      R.run(cells, hyp, mean, out.data(), false, false);
+    }
+    // nothing was written so far: every output in one go, once all cells are done
+    if (T > 0) {
+      HC(hipMemcpyAsync(fs, md.fs, T * 8, hipMemcpyDeviceToHost, st));
+      HC(hipMemcpyAsync(sd, md.var, T * 8, hipMemcpyDeviceToHost, st));
+      if (want_cov) HC(hipMemcpyAsync(cov, md.cov, coffs[ncell] * 8, hipMemcpyDeviceToHost, st));
+      HC(hipStreamSynchronize(st));
+    }
+    for (int64_t c = 0; c < ncell; ++c) {
+      status[c] = out[c].status;
+      const bool bad = out[c].status != 0;  // NB1's LinAlgError
+      for (int64_t a = toffs[c]; a < toffs[c + 1]; ++a) {
+        if (bad) fs[a] = NAN;
+        sd[a] = bad ? NAN : std::sqrt(sd[a]);  // the returned diagonal's root, NaN below 0 as np.sqrt
+      }
+      if (bad && want_cov)
+        for (int64_t e = coffs[c]; e < coffs[c + 1]; ++e) cov[e] = NAN;
     }
     return 0;
   });

@@ -12,6 +12,11 @@ cell 5) fits and predicts with:
   -- NB1 GPR (fs, sd[, prior sd]); ``M=None`` means ``int(n/5)`` as in NB1.
   With ``approx=False`` ``xs`` may be NB1's ns x 3 array of targets
   (``oi_gpr_predict_multi``); ``approx=True`` takes one target per call.
+* ``GPR_multi(x, y, xs, ell, sf2, sn2, mean, M=None, returnprior=False, cov=False)``
+  / ``GPR_multi_batch`` / ``fit_predict_multi_batch`` -- GPR(approx=True) with
+  NB1's ns x 3 targets and, on request, the posterior covariance NB1 forms
+  before taking its diagonal (``oi_nystrom_predict_multi``: the per-cell
+  set-up once, not once per target).
 * ``fit(x, y, M, x0=None)`` / ``fit_batch`` -- ``scipy.optimize.minimize(SMLII, x0,
   args=(x, y, True, M), method='CG', jac=True)`` (NB1 code cell 5) on the
   restated scipy CG of liboi.
@@ -93,10 +98,43 @@ def GPR_batch(xyt, y, offs, xs, hyp, mean, M=None):
     return pred, status
 
 
+def GPR_multi_batch(xyt, y, offs, xs, toffs, hyp, mean, M=None, cov=False):
+    """NB1 GPR(approx=True) with ns x 3 targets, for ragged cells in one liboi
+    call (``oi_nystrom_predict_multi``): cell c predicts at rows
+    toffs[c]:toffs[c+1] of ``xs`` [T x 3].  Returns (fs [T], sd [T], cov, status
+    [ncell]); ``cov`` is None, or with ``cov=True`` the list of the cells' nt x nt
+    posterior covariances ``Kxs - err`` (NB1 GPR before its ``.diagonal()``).
+    ``hyp`` [ncell x 5] LINEAR hypers; ``M`` None => int(n/5) per cell (NB1).
+    NaN in sd (err above Kxs) is NB1's result, not a failure."""
+    sizes = np.diff(np.asarray(offs, dtype=np.int64))
+    if M is None:
+        M = np.array([int(n / 5) for n in sizes], dtype=np.int64)
+    sel, soffs = _ragged_sel(offs, M)
+    fs, sd, flat, status = _lib.nystrom_predict_multi(xyt, y, offs, sel, soffs, hyp, xs, toffs, mean=mean,
+                                                      cov=cov, **options)
+    return fs, sd, (_lib.split_cov(flat, toffs) if cov else None), status
+
+
+def GPR_multi(x, y, xs, ell, sf2, sn2, mean, M=None, returnprior=False, cov=False):
+    """NB1 GPR(approx=True) for one cell at ``xs`` [ns x 3]: (fs [ns x 1], sd
+    [ns][, prior sd][, cov [ns x ns]]) -- NB1's shapes, with the covariance
+    NB1 forms and drops appended on request.  LinAlgError where NB1 raises."""
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    xs = np.asarray(xs, dtype=np.float64).reshape(-1, 3)
+    hyp = np.array([[ell[0], ell[1], ell[2], sf2, sn2]], dtype=np.float64)
+    fs, sd, covs, status = GPR_multi_batch(x, y, [0, len(y)], xs, [0, len(xs)], hyp, mean,
+                                           M=None if M is None else [M], cov=cov)
+    if status[0] != 0:
+        raise np.linalg.LinAlgError("Nystrom / Cholesky factorisation failed")
+    out = (fs.reshape(-1, 1), sd) + ((np.sqrt(sf2),) if returnprior else ())
+    return out + ((covs[0],) if cov else ())
+
+
 def GPR(x, y, xs, ell, sf2, sn2, mean, approx=False, M=None, returnprior=False):
     """NB1 GPR for one cell: (fs, sd[, prior sd]).  ``xs`` is one target or,
     with ``approx=False``, NB1's ns x 3 array of targets (fs and sd of length
-    ns, through ``oi_gpr_predict_multi``)."""
+    ns, through ``oi_gpr_predict_multi``); ``GPR_multi`` takes many targets
+    with ``approx=True``."""
     x = np.asarray(x, dtype=np.float64).reshape(-1, 3)
     y = np.asarray(y, dtype=np.float64).reshape(-1)
     xs = np.asarray(xs, dtype=np.float64).reshape(-1, 3)
@@ -106,7 +144,7 @@ def GPR(x, y, xs, ell, sf2, sn2, mean, approx=False, M=None, returnprior=False):
     if ns != 1:
         if approx:
             raise NotImplementedError("GPR(approx=True) predicts one target per call; "
-                                      f"got xs with {ns} rows (use approx=False, or call per target)")
+                                      f"got xs with {ns} rows (use GPR_multi, or approx=False)")
         # the residual outputs with mean 0, the prior mean added back as in NB1
         f0, sd, _, _, status = _lib.gpr_predict_multi(x, y, offs, xs, [0, ns], 0.0, hyp, lz=False,
                                                       **options)
@@ -148,6 +186,20 @@ def fit_batch(xyt, y, offs, M, x0=None):
     ncell = len(offs) - 1
     _, x, info = fit_predict_batch(xyt, y, offs, np.zeros((ncell, 3)), 0.0, M, x0=x0)
     return x, info
+
+
+def fit_predict_multi_batch(xyt, y, offs, xs, toffs, mean, M, x0=None, cov=False):
+    """``fit_batch`` followed by ``GPR_multi_batch`` at the fitted hypers: NB1
+    code cell 5 with a list of targets per cell.  Returns (fs [T], sd [T], cov,
+    status [ncell], x [ncell x 5] fitted log-hypers, info [ncell x 4])."""
+    offs = np.asarray(offs, dtype=np.int64)
+    ncell = len(offs) - 1
+    sel, soffs = _ragged_sel(offs, M)
+    x0 = default_x0() if x0 is None else np.asarray(x0, dtype=np.float64)
+    out, _, info = _lib.nystrom_fit_batch(xyt, y, offs, sel, soffs, x0, np.zeros((ncell, 3)), 0.0, **options)
+    # the LINEAR hypers as the fit itself predicts with them (no log / exp round trip)
+    fs, sd, covs, status = GPR_multi_batch(xyt, y, offs, xs, toffs, out[:, 3:], mean, M=M, cov=cov)
+    return fs, sd, covs, status, np.log(out[:, 3:]), info
 
 
 def fit(x, y, M, x0=None):
