@@ -99,6 +99,13 @@ SIGNATURES_NYSTROM_MULTI = {
                                                 ctypes.POINTER(OiOptions)]),
 }
 
+# and for include/oi_loo.h (tests/test_loo_abi.py)
+SIGNATURES_LOO = {
+    'oi_gpr_loo': (ctypes.c_int, [c_double_p, c_double_p, c_int64_p, ctypes.c_int64, ctypes.c_double,
+                                  c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
+                                  ctypes.POINTER(OiOptions)]),
+}
+
 
 def load():
     """Load liboi.so (once).  Raises OiError when it has not been built."""
@@ -109,7 +116,7 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise OiError(f"{LIB_PATH} not built: run `make -C {_HERE}` (or __graft_entry__.build())")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in {**SIGNATURES, **SIGNATURES_NYSTROM_MULTI}.items():
+        for name, (restype, argtypes) in {**SIGNATURES, **SIGNATURES_NYSTROM_MULTI, **SIGNATURES_LOO}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -287,6 +294,42 @@ def gpr_predict_multi(xyt, z, offs, xs, toffs, mean, hyp, cov=False, lz=True, de
 def gpr_predict_multi_device(xyt_dev, z_dev, offs, xs, toffs, mean, hyp, **kw):
     """gpr_predict_multi(..., device_inputs=True)."""
     return gpr_predict_multi(xyt_dev, z_dev, offs, xs, toffs, mean, hyp, device_inputs=True, **kw)
+
+
+def gpr_loo(xyt, z, offs, mean, hyp, lpl=True, device_inputs=False, **opt_kw):
+    """oi_gpr_loo: leave-one-out cross-validation of every cell at LINEAR hypers
+    ``hyp`` [ncell x 5], from one factorisation per cell.  Returns (mu [N],
+    sd [N], lpl [ncell] | None, status [ncell]): ``mu[i]`` / ``sd[i]`` are the
+    predictive mean and standard deviation of OBSERVATION i (noise included)
+    given the other observations of its cell, in the observations' own order --
+    the standardised residual is ``(z - mu) / sd`` -- and ``lpl`` the cells' log
+    pseudo-likelihoods.  A cell whose factorisation fails has status 1 and NaN
+    results.  With device_inputs=True ``xyt`` / ``z`` are fp64 contiguous torch
+    tensors on cuda:``device`` and the call runs on torch's current stream;
+    offsets and hypers stay on the host."""
+    offs = _i64(offs)
+    ncell = len(offs) - 1
+    hyp = _f64(hyp).reshape(-1, 5)
+    if hyp.shape[0] != ncell:
+        raise ValueError("hyp must be [ncell x 5]")
+    dev = int(opt_kw.get('device', 0))
+    px, pz, _keep = _obs(xyt, z, offs, device_inputs, dev, what='z')
+    if device_inputs:
+        opt_kw.setdefault('stream', _caller_stream(dev))
+    N = int(offs[-1])
+    mu = np.empty(N)
+    sd = np.empty(N)
+    lpla = np.empty(ncell) if lpl else None
+    status = np.zeros(ncell, dtype=np.int32)
+    o = options(device_inputs=device_inputs, **opt_kw)
+    _check(load().oi_gpr_loo(px, pz, _ptr(offs, ctypes.c_int64), ncell, float(mean), _ptr(hyp), _ptr(mu),
+                             _ptr(sd), _ptr(lpla), _ptr(status, ctypes.c_int32), ctypes.byref(o)))
+    return mu, sd, lpla, status
+
+
+def gpr_loo_device(xyt_dev, z_dev, offs, mean, hyp, **kw):
+    """gpr_loo(..., device_inputs=True)."""
+    return gpr_loo(xyt_dev, z_dev, offs, mean, hyp, device_inputs=True, **kw)
 
 
 def split_cov(cov, toffs):

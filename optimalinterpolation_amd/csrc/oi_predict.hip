@@ -29,6 +29,10 @@
 //
 // All reductions run in a fixed order that depends on the cell alone, so a
 // cell's results do not depend on its batch mates or on the chunking.
+//
+// The second half of the file is oi_gpr_loo (include/oi_loo.h): leave-one-out
+// cross-validation per cell on the same generation, Cholesky and solve, plus
+// the block-column sweep k_loo_sweep over L^-1.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +41,8 @@
 #include <string>
 #include <vector>
 
+#include "../../include/oi_loo.h"
+#include "oi_gemm.h"
 #include "oi_host.h"
 #include "oi_linalg.h"
 #include "oi_matern.h"
@@ -412,6 +418,388 @@ extern "C" int oi_gpr_predict_multi(const double* xyt, const double* z, const in
       HC(hipMemcpyAsync(status + c0, dflag + nc, nc * 4, hipMemcpyDeviceToHost, st));
       if (want_cov && cc > 0) HC(hipMemcpyAsync(cov + covoff, dcov, cc * 8, hipMemcpyDeviceToHost, st));
       covoff += cc;
+      // the next chunk reuses the workspace and the descriptor ring
+      HC(hipStreamSynchronize(st));
+      sg.flush();
+      la.reset();
+    }
+    return 0;
+  });
+}
+
+// ===========================================================================
+// Leave-one-out cross-validation per cell (include/oi_loo.h; Rasmussen &
+// Williams, GPML 5.4.2) at given hypers, from ONE factorisation:
+//
+//   r = z - mean;  K~ = K + sn2 I = L L';  zt = L^-1 r;  W = L^-1
+//   q_c = [K~^-1]_cc = sum_r W_rc^2;  alpha_c = [K~^-1 r]_c = sum_r W_rc zt_r
+//   mu_c = z_c - alpha_c / q_c;  sd_c = sqrt(1 / q_c)
+//   lpl = sum_c [ -log(2 pi)/2 - log sd_c - (z_c - mu_c)^2 / (2 sd_c^2) ]
+//
+// K~ and its factor come from the kernels and oila calls above (PCell with no
+// target); zt is the 1 x n row X through oila::trsm_right_lt.  k_loo_sweep
+// then builds W one 64-column block panel per workgroup and folds every
+// finished 64 x 64 tile into q and alpha; W itself is never kept beyond the
+// panel, and K~^-1 is never formed.
+// ===========================================================================
+namespace {
+
+struct LCell {
+  double* K;           // Np x Np: L below the diagonal blocks; the sweep writes W' = L^-T
+                       // into the strict upper BLOCK triangle (block (j, i), i > j, = W_ij')
+  const double* dinv;  // Np / 64 inverses of L's diagonal blocks (oila::Chol)
+  double* wdt;         // Np / 64 x 4096: their transposes (the panels' first B operand)
+  const double* zt;    // n: L^-1 (z - mean)
+  const double* z;     // n
+  double* mu;          // n
+  double* sd;          // n
+  double* part;        // Np / 64 partial sums of lpl, one per block column
+  double* lpl;         // 1
+  const int32_t* info; // the Cholesky's info
+  int32_t* status;     // 1
+  int n, Np;
+};
+struct LItem {
+  int cell, j;  // one workgroup: block column j of cell `cell` (of the chunk)
+};
+
+typedef __attribute__((address_space(1))) double gdbl;
+typedef __attribute__((address_space(1))) dv2 gdv2w;
+
+#define LOO_LD 72  // LDS row stride of the S / W tile (doubles)
+
+// Block column j of W = L^-1 for one cell, top-down, per 64 x 64 tile
+//   W_jj = Dinv_jj;   W_ij = -Dinv_ii (sum_{k=j}^{i-1} L_ik W_kj),  i > j
+// 256 threads, wave w owns the 32 x 32 quadrant (32 (w >> 1), 32 (w & 1)) as
+// 2 x 2 blocks of v_mfma_f64_16x16x4f64 (the oi_gemm.h layout).
+//   S = sum_k L_ik W_kj is ONE product over the inner index kk = 64 j .. 64 i:
+//   A row kk = L(64 i.., kk) (a column of K, contiguous), B row kk = W(kk, 64 j..)
+//   = the finished tiles' transposes, which this workgroup stored at
+//   K(64 j.., kk) -- also a contiguous column of K (the first 64 kk come from
+//   wdt, the transpose of Dinv_jj).  Chunks 16 deep, two-deep register ring,
+//   two LDS buffers, global-address-space loads, as gemm1_kmajor.
+//   W_ij = -Dinv_ii S: S goes to LDS as the B operand, Dinv_ii (column-major =
+//   k-major) fills the four staging slots as the A operand.
+// Epilogue of every tile, rows r < n only (the pad's identity rows enter no
+// sum), per column c: 16 rows in order per wave-quarter, the four quarters
+// added in order, tiles i ascending -- a fixed order that depends on the cell
+// alone.  The workgroup reads back only what it stored itself, behind a
+// __syncthreads(); no other workgroup touches block row j above the diagonal.
+__global__ void __launch_bounds__(256) k_loo_sweep(const LCell* __restrict__ cs,
+                                                   const LItem* __restrict__ items) {
+  __shared__ __attribute__((aligned(16))) double stg[4 * STAGE_A];  // 2 x (A, B) chunks; then Dinv_ii; then sums
+  __shared__ __attribute__((aligned(16))) double tile[64 * LOO_LD];  // S, then W_ij, [row][column]
+  const LItem item = items[blockIdx.x];
+  const LCell c = cs[item.cell];
+  const int j = item.j, T = c.Np / 64;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, wr = w >> 1, wc = w & 1;
+  const int fr = lane & 15, fk = lane >> 4;
+  const size_t Np = (size_t)c.Np;
+  gdbl* const K = (gdbl*)c.K;
+  const gdbl* const zt = (const gdbl*)c.zt;
+  double qa = 0.0, aa = 0.0;  // threads 0..63: column 64 j + t
+
+  // tile[r][cc] = W_ij[r][cc] is complete: add its columns' sums and store its
+  // transpose at dst[cc + ldd r]
+  auto epilogue = [&](int i, gdbl* dst, size_t ldd) __attribute__((always_inline)) {
+    const int rows = min(64, c.n - 64 * i);
+    const int cc = t & 63;
+    double s2 = 0.0, sz = 0.0;
+    for (int r = 16 * w; r < 16 * w + 16; ++r) {
+      if (r < rows) {
+        const double v = tile[r * LOO_LD + cc];
+        s2 += v * v;
+        sz += v * zt[64 * i + r];
+      }
+    }
+    stg[w * 64 + cc] = s2;
+    stg[256 + w * 64 + cc] = sz;
+    for (int e = t; e < 4096; e += 256) dst[(e & 63) + ldd * (size_t)(e >> 6)] = tile[(e >> 6) * LOO_LD + (e & 63)];
+    __syncthreads();
+    if (t < 64) {
+      qa += ((stg[t] + stg[64 + t]) + stg[128 + t]) + stg[192 + t];
+      aa += ((stg[256 + t] + stg[320 + t]) + stg[384 + t]) + stg[448 + t];
+    }
+    __syncthreads();
+  };
+
+  {  // i = j: W_jj = Dinv_jj (column-major)
+    const gdbl* D = (const gdbl*)c.dinv + (size_t)j * 4096;
+    for (int e = t; e < 4096; e += 256) tile[(e & 63) * LOO_LD + (e >> 6)] = D[e];
+    __syncthreads();
+    epilogue(j, (gdbl*)c.wdt + (size_t)j * 4096, 64);
+  }
+
+  const int sk = t >> 5, sm = (t & 31) * 2;  // this thread's two 16 B pieces of a 16 x 64 chunk: rows sk, sk + 8
+  for (int i = j + 1; i < T; ++i) {
+    const int nch = 4 * (i - j);
+    const double* Ai = c.K + 64 * i;  // A row kk: Ai[m + Np kk]
+    const double* Bj = c.K + 64 * j;  // B row kk >= 64 (j + 1): Bj[n + Np kk]
+    StageRegs r0, r1;
+    auto load = [&](int ch, StageRegs& q) __attribute__((always_inline)) {
+      const size_t kk = (size_t)64 * j + (size_t)KC * ch + sk;
+      const double* pa = Ai + sm + Np * kk;
+      const bool first = ch < 4;  // uniform: rows of W_jj' from wdt
+      const double* pb = first ? c.wdt + (size_t)j * 4096 + sm + 64 * (size_t)(KC * ch + sk) : Bj + sm + Np * kk;
+      const size_t ldb = first ? 64 : Np;
+      q.a0 = gload2(pa);
+      q.a1 = gload2(pa + Np * 8);
+      q.b0 = gload2(pb);
+      q.b1 = gload2(pb + ldb * 8);
+    };
+    auto store = [&](int buf, const StageRegs& q) __attribute__((always_inline)) {
+      double* As = stg + buf * 2 * STAGE_A;
+      double* Bs = As + STAGE_A;
+      *(dv2*)(As + sk * LDSA + sm) = q.a0;
+      *(dv2*)(As + (sk + 8) * LDSA + sm) = q.a1;
+      *(dv2*)(Bs + sk * LDSA + sm) = q.b0;
+      *(dv2*)(Bs + (sk + 8) * LDSA + sm) = q.b1;
+    };
+    Quad acc;
+    quad_zero(acc);
+    auto compute = [&](const double* As, const double* Bs, int ldb, int ksteps) __attribute__((always_inline)) {
+#pragma unroll
+      for (int kq = 0; kq < ksteps; ++kq) {
+        const int k = kq * 4 + fk;
+        const double a0 = As[k * LDSA + 32 * wr + fr];
+        const double a1 = As[k * LDSA + 32 * wr + 16 + fr];
+        const double b0 = Bs[k * ldb + 32 * wc + fr];
+        const double b1 = Bs[k * ldb + 32 * wc + 16 + fr];
+        acc.c[0][0] = MFMA64(a0, b0, acc.c[0][0]);
+        acc.c[0][1] = MFMA64(a0, b1, acc.c[0][1]);
+        acc.c[1][0] = MFMA64(a1, b0, acc.c[1][0]);
+        acc.c[1][1] = MFMA64(a1, b1, acc.c[1][1]);
+      }
+    };
+    // S = sum over kk (nch is a multiple of 4; the prefetches past the end
+    // re-read the last chunk, unused: see gemm2_kmajor)
+    load(0, r0);
+    load(1, r1);
+    store(0, r0);
+    __syncthreads();
+    for (int ch = 0; ch < nch; ch += 2) {
+      load(min(ch + 2, nch - 1), r0);
+      compute(stg, stg + STAGE_A, LDSA, KC / 4);
+      store(1, r1);
+      __syncthreads();
+      load(min(ch + 3, nch - 1), r1);
+      compute(stg + 2 * STAGE_A, stg + 3 * STAGE_A, LDSA, KC / 4);
+      if (ch + 2 < nch) store(0, r0);
+      __syncthreads();
+    }
+    // Dinv_ii (A[m][k] = D[m + 64 k]) into the staging slots, S into the tile
+    {
+      const gdbl* D = (const gdbl*)c.dinv + (size_t)i * 4096;
+      dv2 d[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) d[q] = *(const gdv2w*)(D + 2 * (t + 256 * q));
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int p = t + 256 * q;
+        *(dv2*)(stg + (p >> 5) * LDSA + 2 * (p & 31)) = d[q];
+      }
+    }
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) tile[acc1_row(mb, r) * LOO_LD + acc1_col(nb)] = acc.c[mb][nb][r];
+    __syncthreads();
+    quad_zero(acc);
+    compute(stg, tile, LOO_LD, 16);
+    __syncthreads();
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) tile[acc1_row(mb, r) * LOO_LD + acc1_col(nb)] = -acc.c[mb][nb][r];
+    __syncthreads();
+    epilogue(i, K + 64 * j + Np * 64 * (size_t)i, Np);
+  }
+
+  // mu, sd and this block column's share of lpl (wave 0: one lane per column)
+  if (t < 64) {
+    const int col = 64 * j + t;
+    const bool bad = *c.info != 0;
+    double term = 0.0;
+    if (col < c.n) {
+      const double zc = c.z[col];
+      const double mu = bad ? NAN : zc - aa / qa;
+      const double sd = bad ? NAN : sqrt(1.0 / qa);
+      c.mu[col] = mu;
+      c.sd[col] = sd;
+      const double d = zc - mu;
+      term = ((-LOG2PI / 2.0) - log(sd)) - (d * d) / ((2.0 * sd) * sd);
+    }
+    for (int o = 32; o > 0; o >>= 1) term += __shfl_down(term, o, 64);
+    if (t == 0) c.part[j] = term;
+  }
+}
+
+// lpl = the block columns' partial sums added in index order; status
+__global__ void __launch_bounds__(256) k_loo_finish(const LCell* __restrict__ cs, int nc) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= nc) return;
+  const LCell c = cs[q];
+  double s = 0.0;
+  for (int j = 0; j < c.Np / 64; ++j) s += c.part[j];
+  *c.lpl = s;
+  *c.status = *c.info != 0 ? 1 : 0;
+}
+
+enum { L_GEN, L_CHOL, L_SOLVE, L_SWEEP, L_COUNT };
+const char* kLooStage[L_COUNT] = {"loo_generate", "loo_cholesky", "loo_solve", "loo_sweep"};
+
+// Workspace of one cell in doubles: scaled inputs 3 n, K Np^2 (L below, the
+// panels of W' above the diagonal blocks -- the sweep needs no n x n array of
+// its own), the diagonal-block inverses and their transposes 2 x 64 Np, zt n,
+// lpl partials Np / 64, mu + sd 2 n, inputs 4 n (host inputs only), lpl + flags 2
+int64_t loo_cell_doubles(int64_t n, bool host_inputs) {
+  const int64_t Np = up(n, 64);
+  return up(3 * n, 32) + Np * Np + 2 * Np * 64 + up(n, 32) + up(Np / 64, 32) + 2 * n + (host_inputs ? 4 * n : 0) + 2;
+}
+
+}  // namespace
+
+extern "C" int oi_gpr_loo(const double* xyt, const double* z, const int64_t* offs, int64_t ncell,
+                          double mean, const double* hyp, double* mu, double* sd, double* lpl,
+                          int32_t* status, const oi_options* opts) {
+  if (int rc = oi_check_offs(offs, ncell, 0, "offs")) return rc;
+  if (ncell == 0) return 0;
+  const int64_t N = offs[ncell];
+  if (!status) return oi_set_last_error(OI_E_ARG, "null status");
+  if (!hyp) return oi_set_last_error(OI_E_ARG, "null hyp");
+  if (N > 0 && (!xyt || !z)) return oi_set_last_error(OI_E_ARG, "null xyt / z");
+  if (N > 0 && (!mu || !sd)) return oi_set_last_error(OI_E_ARG, "null mu / sd");
+  constexpr int64_t LIM = 0x7FFFFFF0 / 8;  // oila's operands take 32-bit byte offsets
+  for (int64_t c = 0; c < ncell; ++c) {
+    const int64_t Np = up(offs[c + 1] - offs[c], 64);
+    if (Np * Np >= LIM) return oi_set_last_error(OI_E_ARG, "cell too large (K reaches 2 GiB)");
+  }
+  const oi_options o = oi_resolve(opts);
+  if (int rc = oi_select_device(o)) return rc;
+  return oi_guarded([&] {
+    const bool host_in = o.device_inputs == 0;
+    hipStream_t st = (hipStream_t)o.stream;
+    const auto [cuts, biggest] = plan_chunks(ncell, o, CHUNK_SLACK, CHUNK_CELLS, "leave-one-out", [&](int64_t c) {
+      return loo_cell_doubles(offs[c + 1] - offs[c], host_in);
+    });
+    DevBuf ws((size_t)biggest * 8);
+    oila::Stager la;
+    la.bind(st);
+    StageTimer sg(kLooStage, L_COUNT);
+    sg.on = o.profile != 0;
+    sg.st = st;
+    std::vector<PCell> cells;
+    std::vector<LCell> lcells;
+    std::vector<LItem> items;
+    std::vector<oila::Chol> chol;
+    std::vector<oila::TrsmRLT> trsm;
+    for (size_t q = 0; q + 1 < cuts.size(); ++q) {
+      const int64_t c0 = cuts[q], c1 = cuts[q + 1], nc = c1 - c0;
+      const int64_t n0 = offs[c0], nn = offs[c1] - n0;
+      Carver cv{static_cast<double*>(ws.p)};
+      const double* dx = xyt ? xyt + n0 * 3 : nullptr;
+      const double* dz = z ? z + n0 : nullptr;
+      if (host_in && nn > 0) {
+        double* hx = cv.take(nn * 3);
+        double* hz = cv.take(nn);
+        HC(hipMemcpyAsync(hx, xyt + n0 * 3, nn * 3 * 8, hipMemcpyHostToDevice, st));
+        HC(hipMemcpyAsync(hz, z + n0, nn * 8, hipMemcpyHostToDevice, st));
+        dx = hx;
+        dz = hz;
+      }
+      double* dmu = cv.take(nn);
+      double* dsd = cv.take(nn);
+      double* dlpl = cv.take(nc);
+      int32_t* dflag = reinterpret_cast<int32_t*>(cv.take(nc));  // info [nc], status [nc]
+      HC(hipMemsetAsync(dflag, 0, nc * 8, st));
+      cells.clear();
+      lcells.clear();
+      items.clear();
+      chol.clear();
+      trsm.clear();
+      int64_t nmax = 0;
+      double fl = 0.0, fl_solve = 0.0, by_gen = 0.0;
+      for (int64_t c = c0; c < c1; ++c) {
+        const int64_t n = offs[c + 1] - offs[c], Np = up(n, 64);
+        const double* h = hyp + c * 5;
+        PCell p{};
+        p.x = dx ? dx + (offs[c] - n0) * 3 : nullptr;
+        p.z = dz ? dz + (offs[c] - n0) : nullptr;
+        p.sc = cv.take(3 * n);
+        p.K = cv.take(Np * Np);
+        double* dinv = cv.take(Np * 64);
+        double* wdt = cv.take(Np * 64);
+        p.X = cv.take(n);  // nt = 0: the one row z - mean, then zt
+        double* part = cv.take(Np / 64);
+        p.info = dflag + (c - c0);
+        p.status = dflag + nc + (c - c0);
+        p.n = (int)n;
+        p.nt = 0;
+        p.Np = (int)Np;
+        p.l0 = h[0];
+        p.l1 = h[1];
+        p.l2 = h[2];
+        p.sf2 = h[3];
+        p.sn2 = h[4];
+        p.mean = mean;
+        cells.push_back(p);
+        lcells.push_back(LCell{p.K, dinv, wdt, p.X, p.z, dmu + (offs[c] - n0), dsd + (offs[c] - n0), part,
+                               dlpl + (c - c0), p.info, p.status, p.n, p.Np});
+        if (n > 0) {
+          chol.push_back(oila::Chol{p.K, dinv, p.info, p.Np, p.Np});
+          trsm.push_back(oila::TrsmRLT{p.X, p.K, dinv, 1, p.n, 1, p.Np});
+        }
+        for (int j = 0; j < (int)(Np / 64); ++j) items.push_back(LItem{(int)(c - c0), j});
+        nmax = std::max(nmax, n);
+        const double dn = (double)n;
+        fl += dn * dn * dn / 3.0;
+        fl_solve += dn * dn;
+        by_gen += 8.0 * (dn * dn / 2.0 + dn);
+      }
+      if (cv.off > biggest) throw HipErr{"oi_gpr_loo: workspace layout exceeds its estimate"};
+      // the longest block columns first (j ascending: Np / 64 - j tiles each);
+      // ties keep the cells' order
+      std::stable_sort(items.begin(), items.end(), [&](const LItem& a, const LItem& b) {
+        return lcells[a.cell].Np / 64 - a.j > lcells[b.cell].Np / 64 - b.j;
+      });
+      const PCell* dc = la.put(cells);
+      const LCell* dl = la.put(lcells);
+      const unsigned gz = (unsigned)nc, Tn = blocks(nmax, 64);
+      sg.begin(L_GEN, 0.0, by_gen);
+      if (nmax > 0) {
+        hipLaunchKernelGGL(k_pm_scale, dim3(blocks(nmax, 256), gz), dim3(256), 0, st, dc);
+        KCHK();
+        hipLaunchKernelGGL(k_pm_kgen, dim3(Tn, Tn, gz), dim3(256), 0, st, dc);
+        KCHK();
+        hipLaunchKernelGGL(k_pm_xgen, dim3(blocks(nmax, 256), gz), dim3(256), 0, st, dc);
+        KCHK();
+      }
+      sg.end();
+      sg.begin(L_CHOL, fl, 0.0);
+      oila::cholesky(la, st, chol);
+      sg.end();
+      sg.begin(L_SOLVE, fl_solve, 0.0);
+      oila::trsm_right_lt(la, st, trsm);
+      sg.end();
+      sg.begin(L_SWEEP, fl, 0.0);
+      if (!items.empty()) {
+        const LItem* di = la.put(items);
+        hipLaunchKernelGGL(k_loo_sweep, dim3((unsigned)items.size()), dim3(256), 0, st, dl, di);
+        KCHK();
+      }
+      hipLaunchKernelGGL(k_loo_finish, dim3(blocks(nc, 256)), dim3(256), 0, st, dl, (int)nc);
+      KCHK();
+      sg.end();
+      if (nn > 0) {
+        HC(hipMemcpyAsync(mu + n0, dmu, nn * 8, hipMemcpyDeviceToHost, st));
+        HC(hipMemcpyAsync(sd + n0, dsd, nn * 8, hipMemcpyDeviceToHost, st));
+      }
+      if (lpl) HC(hipMemcpyAsync(lpl + c0, dlpl, nc * 8, hipMemcpyDeviceToHost, st));
+      HC(hipMemcpyAsync(status + c0, dflag + nc, nc * 4, hipMemcpyDeviceToHost, st));
       // the next chunk reuses the workspace and the descriptor ring
       HC(hipStreamSynchronize(st));
       sg.flush();

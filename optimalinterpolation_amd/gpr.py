@@ -149,3 +149,24 @@ def gpr_cells_multi(cells, xs, toffs, opt=True, x0=None, hyp=None, cov=False, **
     fs, sd, _, cv, st = _lib.gpr_predict_multi(cells.xyt, cells.z, cells.offs, xs, toffs, cells.mean,
                                                h, cov=cov, lz=False, **o)
     return fs, sd, (_lib.split_cov(cv, toffs) if cov else None), out8, np.maximum(status, st)
+
+
+def loo_cells(cells, opt=True, x0=None, hyp=None, **kw):
+    """Leave-one-out cross-validation of every cell of a RaggedCells object
+    (``oi_gpr_loo``: one factorisation per cell, not one per observation).
+
+    ``opt=True`` fits the hypers exactly as ``gpr_cells(opt=True)`` does (one
+    ``oi_gpr_batch`` call, results unchanged) and cross-validates at the fitted
+    hypers; ``opt=False`` does so at ``hyp`` [ncell x 5].  Returns ``(mu [N],
+    sd [N], lpl [ncell], out8, status)``: ``mu[i]`` / ``sd[i]`` predict
+    observation i (noise included) from the other observations of its cell, so
+    the standardised residual is ``(cells.z - mu) / sd``; ``lpl`` is the log
+    pseudo-likelihood per cell, ``out8`` what ``gpr_cells`` returns, and
+    ``status[c]`` the maximum of the fit's and the cross-validation's (non-zero:
+    a covariance was not positive definite, NaN outputs)."""
+    o = dict(options)
+    o.update(kw)
+    out8, status, _ = gpr_cells(cells, opt=opt, x0=x0, hyp=hyp, **kw)
+    h = out8[:, 3:8] if opt else np.asarray(hyp, dtype=np.float64).reshape(-1, 5)
+    mu, sd, lpl, st = _lib.gpr_loo(cells.xyt, cells.z, cells.offs, cells.mean, h, **o)
+    return mu, sd, lpl, out8, np.maximum(status, st)

@@ -17,6 +17,9 @@ cell 5) fits and predicts with:
   NB1's ns x 3 targets and, on request, the posterior covariance NB1 forms
   before taking its diagonal (``oi_nystrom_predict_multi``: the per-cell
   set-up once, not once per target).
+* ``GPR_loo(x, y, ell, sf2, sn2, mean)`` -- not in NB1: leave-one-out
+  cross-validation of the full GP at the hypers NB1's GPR takes (mu, sd, log
+  pseudo-likelihood; ``oi_gpr_loo``, one factorisation).
 * ``fit(x, y, M, x0=None)`` / ``fit_batch`` -- ``scipy.optimize.minimize(SMLII, x0,
   args=(x, y, True, M), method='CG', jac=True)`` (NB1 code cell 5) on the
   restated scipy CG of liboi.
@@ -158,6 +161,22 @@ def GPR(x, y, xs, ell, sf2, sn2, mean, approx=False, M=None, returnprior=False):
     if status[0] != 0:
         raise np.linalg.LinAlgError("Nystrom / Cholesky factorisation failed")
     return (fs, sd, sp) if returnprior else (fs, sd)
+
+
+def GPR_loo(x, y, ell, sf2, sn2, mean):
+    """Leave-one-out cross-validation of one cell of the full GP in NB1 GPR's
+    argument style (``y`` the residual outputs, ``mean`` added back): (mu [n],
+    sd [n], lpl).  ``mu[i]`` / ``sd[i]`` predict output i (noise included) from
+    the others, so the standardised residual is ``(y + mean - mu) / sd``;
+    ``lpl`` is the log pseudo-likelihood.  LinAlgError where the Cholesky
+    factorisation fails (``oi_gpr_loo``)."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1, 3)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    hyp = np.array([[ell[0], ell[1], ell[2], sf2, sn2]], dtype=np.float64)
+    mu, sd, lpl, status = _lib.gpr_loo(x, y, [0, len(y)], 0.0, hyp, **options)
+    if status[0] != 0:
+        raise np.linalg.LinAlgError("Cholesky factorisation failed")
+    return mean + mu, sd, lpl[0]
 
 
 def default_x0(grid_res=25):
