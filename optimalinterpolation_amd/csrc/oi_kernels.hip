@@ -1817,6 +1817,9 @@ static inline hipStream_t S(void* s) { return (hipStream_t)s; }
 static inline int ret() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 static inline unsigned grid1(int gx, int ncell) { return (unsigned)gx * (unsigned)((ncell + 7) & ~7); }
 
+// sizeof(OiCell) as compiled, for the ctypes mirror of tests/dense_ref.py
+extern "C" int oi_test_sizeof_cell(void) { return (int)sizeof(OiCell); }
+
 extern "C" int oi_launch_diag_factor(const OiCell* cells, const int32_t* list, int ncell, int j,
                                      void* stream) {
   if (ncell <= 0) return 0;

@@ -12,6 +12,7 @@ import pytest
 from scipy.spatial.distance import pdist, squareform
 
 from conftest import load_golden, ragged_cell
+from dense_ref import exact_cell, exact_cells, site_counts
 from oracle import gp_oracle as O
 from optimalinterpolation_amd import _lib, synthetic
 
@@ -67,9 +68,13 @@ def test_smlii_golden():
 
 @pytest.mark.parametrize('n', [63, 64, 65, 130, 333, 700, 1100])
 def test_smlii_vs_oracle_sizes(n):
-    """Tile-boundary sizes and multi-tile cells, 3 hyper points each."""
+    """Tile-boundary sizes and multi-tile cells, 3 hyper points each.  n is the
+    number of distinct SITES, which is what the kernels tile (two cells
+    without repeats, one with n sites under n + max(3, n / 10) observations:
+    the site form's (n - m) and SSW terms on the same edge)."""
     rng = np.random.default_rng(n)
-    cells = synthetic.make_cells([n] * 3, seed=n)
+    cells = exact_cells([n, n, (n, n + max(3, n // 10))], seed=n)
+    assert [q[1] for q in site_counts(cells)] == [n] * 3
     hs = np.array([O.X0_PRODUCTION,
                    [np.log(3e5), np.log(2e5), np.log(8.), np.log(4e-3), np.log(5e-4), 0.0],
                    [np.log(9e4), np.log(1.5e5), np.log(3.), np.log(1e-2), np.log(2e-3), -2.0]])
@@ -160,9 +165,13 @@ def test_gpr3d_n0_edge():
 
 
 def _check_tile_boundary_sizes():
-    """SMLII and the predict block meet the T1 tolerance on tile-boundary sizes."""
-    sizes = [63, 64, 65, 129, 200, 257, 700]
-    cells = synthetic.make_cells(sizes, seed=11)
+    """SMLII and the predict block meet the T1 tolerance on tile-boundary sizes:
+    site counts m = 63 .. 700 (T = 1, 1, 2, 3, 4, 5, 11 block rows, the last
+    with 63, 64, 1, 1, 8, 1, 60 rows) and one cell of 129 sites under 150
+    observations (the deduplicated path)."""
+    sizes = [63, 64, 65, 129, 200, 257, 700, (129, 150)]
+    cells = exact_cells(sizes, seed=11)
+    assert [q[1] for q in site_counts(cells)] == [63, 64, 65, 129, 200, 257, 700, 129]
     h = np.tile(np.array([np.log(2e5), np.log(2.5e5), np.log(7.), np.log(4e-3), np.log(1e-3), 0.]),
                 (len(sizes), 1))
     mX = np.full(len(cells.z), cells.mean)
@@ -193,21 +202,28 @@ def test_panels_tile_boundary_sizes():
 @pytest.mark.parametrize('knob,value', [('OI_PANEL4', '0'), ('OI_PANEL4_MINT', '0')])
 def test_alternate_kernels_agree(knob, value, monkeypatch):
     """The even-column panel core the engine selects per round -- k_panel_even
-    everywhere (OI_PANEL4=0) or k_panel4 in every round (OI_PANEL4_MINT=0; by
-    default only in rounds whose largest cell has >= 12 block columns) --
+    everywhere (OI_PANEL4=0) or k_panel4 in every round (OI_PANEL4_MINT=0 with
+    OI_PANEL4_MINWG=0; by default only in rounds whose largest cell has >= 12
+    block columns and in launches of >= 512 workgroups, which these few cells
+    of at most 11 block rows never reach) --
     meets the T1 tolerance on tile-boundary sizes, fit and predict.  (Round 4
     retired the other A/B alternates -- round 1's 32-blocked and round 2's
     single-wave diagonal factors, the P-form panels with k_scale, the 128x128
     K^-1 kernel and the folded pair step)"""
     monkeypatch.setenv(knob, value)
+    if knob == 'OI_PANEL4_MINT':
+        monkeypatch.setenv('OI_PANEL4_MINWG', '0')
     _check_tile_boundary_sizes()
 
 
 def test_config5_size_n5000():
-    """BASELINE config 5 allows n up to 5000 per cell (T = 79 tiles): SMLII and
-    the predict block at that size, T1 tolerance, one cell each."""
+    """BASELINE config 5 allows n up to 5000 per cell: SMLII and the predict
+    block at 5000 distinct sites (T = 79 block rows, the last with 8; off the
+    25 km lattice, which holds only ~4070 sites per cell), T1 tolerance, one
+    cell each."""
     n = 5000
-    cells = synthetic.make_cells([n], seed=5000)
+    cells = exact_cell(n, n, seed=5000, lattice=False)
+    assert site_counts(cells) == [(5000, 5000, 79, 8)]
     h = np.array([[np.log(2.2e5), np.log(1.8e5), np.log(6.), np.log(5e-3), np.log(1e-3), 0.0]])
     mX = np.full(n, cells.mean)
     nlz, grad, status = _lib.nlml_grad_batch(cells.xyt, cells.z, mX, cells.offs, h)
@@ -234,7 +250,8 @@ def test_duplicate_sites_reduction():
     SSW terms added back -- exact algebra, so nlZ / gradient / predict agree
     with the oracle's n x n computation (GPR:107-141, 173-182) at T1, with
     deduplication on (default) and off (OI_DEDUP=0), including a cell beyond
-    the kernel's LDS staging size (n = 4500) and one made only of copies of a
+    k_dedup's LDS staging size (4500 observations on 2820 sites: T = 45 block
+    rows deduplicated, 71 with OI_DEDUP=0) and one made only of copies of a
     single site."""
     import os
     rng = np.random.default_rng(8)
@@ -324,8 +341,9 @@ def test_panel4_equals_panel_even(monkeypatch):
     predictions are BITWISE equal, so the engine's per-round choice between
     them never changes a result; poisoned workspaces (OI_POISON=1) included --
     nothing is read before it is written."""
-    sizes = [1, 40, 63, 64, 65, 128, 129, 191, 192, 193, 257, 700, 1100, 2000]
-    cells = synthetic.make_cells(sizes, seed=23)
+    sizes = [1, 40, 63, 64, 65, 128, 129, 191, 192, 193, 257, 700, 1100, 2000, (193, 230)]   # site counts
+    cells = exact_cells(sizes, seed=23)
+    assert [q[1] for q in site_counts(cells)] == [s if np.ndim(s) == 0 else s[0] for s in sizes]
     h = np.tile(np.array([np.log(2e5), np.log(2.5e5), np.log(7.), np.log(4e-3), np.log(1e-3), 0.]), (len(sizes), 1))
     mX = np.full(len(cells.z), cells.mean)
     hyp = np.tile(synthetic.FIXED_HYPERS, (len(sizes), 1))
@@ -353,8 +371,9 @@ def test_fused_diag_factor_equals_separate_launches(monkeypatch):
     k_diag_factor4w launch instead.  Same arithmetic on the same
     LDS layout: objective, gradient, predictions and a full fit bitwise equal,
     for both even-column kernels."""
-    sizes = [1, 63, 64, 65, 129, 192, 257, 700, 1100, 2000]
-    cells = synthetic.make_cells(sizes, seed=29)
+    sizes = [1, 63, 64, 65, 129, 192, 257, 700, 1100, 2000, (257, 300)]   # site counts
+    cells = exact_cells(sizes, seed=29)
+    assert [q[1] for q in site_counts(cells)] == [s if np.ndim(s) == 0 else s[0] for s in sizes]
     h = np.tile(np.array([np.log(2e5), np.log(2.5e5), np.log(7.), np.log(4e-3), np.log(1e-3), 0.]), (len(sizes), 1))
     mX = np.full(len(cells.z), cells.mean)
     hyp = np.tile(synthetic.FIXED_HYPERS, (len(sizes), 1))
