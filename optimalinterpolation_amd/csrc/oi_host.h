@@ -163,16 +163,37 @@ struct OwnStream {
   }
 };
 
-// Carves 256-byte-aligned arrays of doubles out of one workspace.
+// Carves 256-byte-aligned arrays of doubles out of one workspace.  A path
+// writes its arrays once, as a layout function over a Carver; without a base
+// the same function only counts (take returns null, off is the size), so a
+// workspace's size is never a second description of it.  quantum 1 counts a
+// cell's share of chunk-wide arrays, which hold the cells' parts back to back
+// and are rounded once per chunk (the planner's slack).
 struct Carver {
-  double* base;
+  double* base = nullptr;
   int64_t off = 0;
+  int64_t quantum = 32;
   double* take(int64_t doubles) {
-    double* p = base + off;
-    off += up(doubles, 32);
+    double* p = base ? base + off : nullptr;
+    off += up(doubles, quantum);
     return p;
   }
 };
+
+// `count` doubles of a host array into the workspace (asynchronous on st);
+// null, with nothing taken, for an empty array
+inline double* stage_host(Carver& cv, const double* src, int64_t count, hipStream_t st) {
+  if (count <= 0) return nullptr;
+  double* p = cv.take(count);
+  if (p) HC(hipMemcpyAsync(p, src, count * 8, hipMemcpyHostToDevice, st));
+  return p;
+}
+
+// A cell's workspace in doubles, from the path's layout on a counting Carver
+// (oi_svgp_predict.hip, oi_nystrom.hip); the test hook oi_test_cell_doubles
+// in oi_predict.hip hands them out with its own two.
+int64_t oi_svgp_cell_doubles(int M, int64_t n, bool cov, bool host_inputs, bool elbo);
+int64_t oi_nystrom_multi_cell_doubles(int64_t n, int64_t M, int64_t nt, bool cov);
 
 // The workspace budget in doubles: opts.pool_bytes, or 60 % of the free HBM.
 inline int64_t oi_workspace_budget(const oi_options& o) {

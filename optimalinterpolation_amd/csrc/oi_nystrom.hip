@@ -538,11 +538,35 @@ struct MultiDev {
   double* var = nullptr;           // [T] diag(Kxs - err)
   double* cov = nullptr;           // [coffs[ncell]] or null
   double *ts = nullptr, *KxT = nullptr, *VT = nullptr, *Kp = nullptr, *Vp = nullptr;
-  // doubles of one cell's scratch: scaled targets, Kxsx' (nt x n), V' (nt x M)
-  // and their zero-padded k-major tiles
-  static int64_t cell_doubles(int64_t n, int64_t M, int64_t nt) {
-    const int64_t Tt = (nt + 63) / 64;
-    return up(3 * nt, 32) + up(nt * n, 32) + up(nt * M, 32) + ((n + 63) / 64 + (M + 63) / 64) * Tt * 4096;
+
+  // One cell's scratch in doubles, array by array: scaled targets, Kxsx'
+  // (nt x n), V' (nt x M) and their zero-padded k-major tiles.
+  struct Scratch {
+    int64_t ts = 0, KxT = 0, VT = 0, Kp = 0, Vp = 0;
+    void grow(int64_t n, int64_t M, int64_t nt) {
+      const int64_t Tt = (nt + 63) / 64;
+      ts = std::max(ts, 3 * nt), KxT = std::max(KxT, nt * n), VT = std::max(VT, nt * M);
+      Kp = std::max(Kp, (n + 63) / 64 * Tt * 4096), Vp = std::max(Vp, (M + 63) / 64 * Tt * 4096);
+    }
+  };
+  // The workspace, described once: the call's T targets and outputs (covd
+  // covariance elements, none if negative), then one cell's scratch.  On a
+  // counting Carver: the size of the call, or (T = 0) of one cell's scratch.
+  void layout(Carver& cv, int64_t T, int64_t covd, const Scratch& s, const double* xs_host, hipStream_t st) {
+    xs = stage_host(cv, xs_host, 3 * T, st);
+    fs = cv.take(T);
+    var = cv.take(T);
+    cov = covd >= 0 ? cv.take(covd) : nullptr;
+    ts = cv.take(s.ts);
+    KxT = cv.take(s.KxT);
+    VT = cv.take(s.VT);
+    Kp = cv.take(s.Kp);
+    Vp = cv.take(s.Vp);
+  }
+  static int64_t doubles(int64_t T, int64_t covd, const Scratch& s) {
+    Carver cv;
+    MultiDev().layout(cv, T, covd, s, nullptr, nullptr);
+    return cv.off;
   }
 };
 
@@ -1141,6 +1165,13 @@ extern "C" int oi_nystrom_batch(const double* xyt, const double* y, const int64_
   });
 }
 
+// one cell's scratch, and its covariance as it lies among the call's (not rounded)
+int64_t oi_nystrom_multi_cell_doubles(int64_t n, int64_t M, int64_t nt, bool cov) {
+  MultiDev::Scratch s;
+  s.grow(n, M, nt);
+  return MultiDev::doubles(0, -1, s) + (cov ? nt * nt : 0);
+}
+
 extern "C" int oi_nystrom_predict_multi(const double* xyt, const double* y, const int64_t* offs,
                                         int64_t ncell, const int64_t* sel, const int64_t* soffs,
                                         const double* hyp, const double* xs, const int64_t* toffs,
@@ -1172,39 +1203,25 @@ extern "C" int oi_nystrom_predict_multi(const double* xyt, const double* y, cons
     const bool want_cov = cov != nullptr;
     // one cell's scratch (n x nt, M x nt and their tiles), the call's targets and outputs
     const int64_t budget = oi_workspace_budget(o);
-    int64_t tsd = 0, kxd = 0, vtd = 0, kpd = 0, vpd = 0;  // each scratch array at its largest
+    MultiDev::Scratch big;  // each scratch array at its largest
     for (int64_t c = 0; c < ncell; ++c) {
       const int64_t n = offs[c + 1] - offs[c], M = soffs[c + 1] - soffs[c], nt = toffs[c + 1] - toffs[c];
-      const int64_t Tt = (nt + 63) / 64;
-      if (MultiDev::cell_doubles(n, M, nt) + (want_cov ? nt * nt : 0) > budget)
+      if (oi_nystrom_multi_cell_doubles(n, M, nt, want_cov) > budget)
         throw NoMem{"a cell's Nystrom prediction workspace does not fit pool_bytes"};
-      tsd = std::max(tsd, 3 * nt);
-      kxd = std::max(kxd, nt * n);
-      vtd = std::max(vtd, nt * M);
-      kpd = std::max(kpd, (n + 63) / 64 * Tt * 4096);
-      vpd = std::max(vpd, (M + 63) / 64 * Tt * 4096);
+      big.grow(n, M, nt);
     }
-    const int64_t total = up(tsd, 32) + up(kxd, 32) + up(vtd, 32) + kpd + vpd + up(3 * T, 32) +
-                          2 * up(T, 32) + (want_cov ? up(coffs[ncell], 32) : 0);
+    const int64_t covd = want_cov ? coffs[ncell] : -1;
+    const int64_t total = MultiDev::doubles(T, covd, big);
     if (total > budget)
       throw NoMem{"the call's targets and covariances do not fit pool_bytes: pass fewer cells per call"};
     DevBuf ws((size_t)total * 8);
     Carver cv{static_cast<double*>(ws.p)};
-    double* dxs = cv.take(3 * T);
     MultiDev md;
-    md.xs = dxs;
     md.toffs = toffs;
     md.coffs = coffs.data();
-    md.fs = cv.take(T);
-    md.var = cv.take(T);
-    md.cov = want_cov ? cv.take(coffs[ncell]) : nullptr;
-    md.ts = cv.take(tsd);
-    md.KxT = cv.take(kxd);
-    md.VT = cv.take(vtd);
-    md.Kp = cv.take(kpd);
-    md.Vp = cv.take(vpd);
+    md.layout(cv, T, covd, big, xs, st);
+    if (cv.off > total) throw HipErr{"oi_nystrom_predict_multi: workspace layout exceeds its estimate"};
     BatchDev bd(b, nullptr, o.device_inputs != 0, st);
-    if (T > 0) HC(hipMemcpyAsync(dxs, xs, T * 3 * 8, hipMemcpyHostToDevice, st));
     std::vector<CellOut> out(ncell);
     {
       Runner R(&bd.rows, b.nmax, b.mmax, ncell, o, false, false);

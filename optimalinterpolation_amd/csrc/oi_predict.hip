@@ -243,20 +243,165 @@ __global__ void __launch_bounds__(256) k_pm_reduce(const PCell* __restrict__ cs)
 enum { S_GEN, S_CHOL, S_SOLVE, S_REDUCE, S_COV, S_COUNT };
 const char* kStage[S_COUNT] = {"pm_generate", "pm_cholesky", "pm_solve", "pm_reduce", "pm_cov"};
 
-// Workspace of one cell in doubles.  Per-cell arrays are rounded to 32 doubles
-// (256 bytes); the chunk-wide arrays (inputs, targets, outputs, cov, flags)
-// are the cells' parts back to back, so their share is not rounded.
-//   scaled inputs / targets 3 (n + nt), K Np^2, the factor's diagonal-block
-//   inverses 64 Np, X (nt + 1) n, cov nt^2, fs + sd 2 nt, targets 3 nt,
-//   inputs 4 n (host inputs only), lZ + flags 2
-int64_t cell_doubles(int64_t n, int64_t nt, bool cov, bool host_inputs) {
-  const int64_t Np = up(n, 64);
-  int64_t d = up(3 * n, 32) + up(3 * nt, 32) + Np * Np + Np * 64 + up((nt + 1) * n, 32);
-  d += (cov ? nt * nt : 0) + 2 * nt + 3 * nt + (host_inputs ? 4 * n : 0) + 2;
-  return d;
-}
 constexpr int64_t CHUNK_SLACK = 8 * 32;  // rounding of the chunk-wide arrays (doubles)
 constexpr int64_t CHUNK_CELLS = 4096;    // cells per chunk at most (launch grids, descriptor arrays)
+
+// The two layout functions below are the one description of both entry points'
+// workspace.  A cell's size for the chunk planner is the same functions on
+// counting Carvers: its own arrays rounded to 32 doubles (256 bytes), plus its
+// unrounded share of the chunk-wide arrays (the cells' parts back to back).
+struct DenseIn {  // the caller's inputs
+  const double *xyt, *z;
+  bool host;  // staged into the workspace chunk by chunk
+  hipStream_t st;
+};
+
+// Chunk-wide, nc cells with nn rows from row n0 and tt targets: inputs 4 nn
+// (host inputs only), targets 3 tt, two outputs of `no` doubles (fs, sd per
+// target; leave-one-out: mu, sd per row), lZ / lpl + flags 2 nc, cov cc or none (< 0)
+struct DenseChunk {
+  const double *x, *z, *xs;
+  double *mu, *sd, *lz;
+  int32_t* flag;  // info [nc], status [nc], zeroed
+  double* cov;
+};
+DenseChunk dense_chunk(Carver& cv, const DenseIn& in, int64_t n0, int64_t nn, const double* xs, int64_t tt,
+                       int64_t no, int64_t nc, int64_t cc) {
+  DenseChunk k{in.xyt ? in.xyt + n0 * 3 : nullptr, in.z ? in.z + n0 : nullptr};
+  if (in.host) {
+    k.x = stage_host(cv, k.x, nn * 3, in.st);
+    k.z = stage_host(cv, k.z, nn, in.st);
+  }
+  k.xs = stage_host(cv, xs, tt * 3, in.st);
+  k.mu = cv.take(no);
+  k.sd = cv.take(no);
+  k.lz = cv.take(nc);
+  k.flag = reinterpret_cast<int32_t*>(cv.take(nc));
+  if (k.flag) HC(hipMemsetAsync(k.flag, 0, nc * 8, in.st));
+  k.cov = cc >= 0 ? cv.take(cc) : nullptr;
+  return k;
+}
+// One cell's own: scaled inputs 3 n and targets 3 nt, K Np^2, the factor's
+// diagonal-block inverses 64 Np, X (nt + 1) n; leave-one-out adds their
+// transposes 64 Np and the lpl partials Np / 64 (the sweep writes the panels of
+// W' into K above the diagonal blocks and needs no n x n array of its own).
+struct DenseCell {
+  double *sc, *xsc, *K, *dinv, *wdt, *X, *part;
+};
+DenseCell dense_cell(Carver& cv, int64_t n, int64_t nt, bool loo) {
+  const int64_t Np = up(n, 64);
+  DenseCell a;
+  a.sc = cv.take(3 * n);
+  a.xsc = cv.take(3 * nt);
+  a.K = cv.take(Np * Np);
+  a.dinv = cv.take(Np * 64);
+  a.wdt = loo ? cv.take(Np * 64) : nullptr;
+  a.X = cv.take((nt + 1) * n);
+  a.part = loo ? cv.take(Np / 64) : nullptr;
+  return a;
+}
+int64_t dense_cell_doubles(int64_t n, int64_t nt, bool cov, bool host_inputs, bool loo) {
+  Carver own, share{nullptr, 0, 1};
+  dense_cell(own, n, nt, loo);
+  dense_chunk(share, DenseIn{nullptr, nullptr, host_inputs, nullptr}, 0, n, nullptr, nt, loo ? n : nt, 1,
+              cov ? nt * nt : -1);
+  return own.off + share.off;
+}
+
+// What oi_gpr_predict_multi and oi_gpr_loo share per chunk: staging, carving,
+// the PCell descriptors, generation, Cholesky and solve; status copy and hand-over.
+struct Front {
+  const DenseIn in;
+  const int64_t* offs;
+  const double* hyp;
+  const double mean;
+  const bool loo;
+  hipStream_t st = in.st;
+  oila::Stager la;
+  StageTimer sg;
+  std::vector<PCell> cells;
+  std::vector<oila::Chol> chol;
+  std::vector<oila::TrsmRLT> trsm;
+  DenseChunk k;    // the chunk's arrays
+  int64_t c0, nc;  // its cells
+  int64_t nmax, ntmax, pts, xel;
+  double fl_chol, fl_solve, by_gen;
+
+  Front(const oi_options& o, const double* xyt, const double* z, const int64_t* offs, const double* hyp, double mean,
+        bool loo, const char* const* stages, int count)
+      : in{xyt, z, o.device_inputs == 0, (hipStream_t)o.stream}, offs(offs), hyp(hyp), mean(mean), loo(loo),
+        sg(stages, count) {
+    la.bind(st);
+    sg.on = o.profile != 0;
+    sg.st = st;
+  }
+  // cells c0 .. c1 - 1 with their tt targets at xs and cc covariance elements
+  void begin(Carver& cv, int64_t c0_, int64_t c1, const double* xs, int64_t tt, int64_t cc) {
+    c0 = c0_;
+    nc = c1 - c0;
+    const int64_t nn = offs[c1] - offs[c0];
+    k = dense_chunk(cv, in, offs[c0], nn, xs, tt, loo ? nn : tt, nc, cc);
+    cells.clear();
+    chol.clear();
+    trsm.clear();
+    nmax = ntmax = pts = xel = 0;
+    fl_chol = fl_solve = by_gen = 0.0;
+  }
+  // the chunk's next cell c: its arrays into a, and its descriptor's common fields
+  PCell& add(Carver& cv, int64_t c, int64_t nt, DenseCell& a) {
+    const int64_t r0 = offs[c] - offs[c0], n = offs[c + 1] - offs[c], q = c - c0;
+    const double* h = hyp + c * 5;
+    a = dense_cell(cv, n, nt, loo);
+    const PCell p{.x = k.x ? k.x + r0 * 3 : nullptr, .z = k.z ? k.z + r0 : nullptr, .sc = a.sc, .K = a.K, .X = a.X,
+                  .info = k.flag + q, .status = k.flag + nc + q, .n = (int)n, .nt = (int)nt, .Np = (int)up(n, 64),
+                  .l0 = h[0], .l1 = h[1], .l2 = h[2], .sf2 = h[3], .sn2 = h[4], .mean = mean};
+    if (n > 0) {
+      chol.push_back(oila::Chol{p.K, a.dinv, p.info, p.Np, p.Np});
+      trsm.push_back(oila::TrsmRLT{p.X, p.K, a.dinv, p.nt + 1, p.n, p.nt + 1, p.Np});
+    }
+    nmax = std::max(nmax, n);
+    ntmax = std::max(ntmax, nt);
+    pts = std::max(pts, n + nt);
+    xel = std::max(xel, (nt + 1) * n);
+    const double dn = (double)n, dt = (double)nt;
+    fl_chol += dn * dn * dn / 3.0;
+    fl_solve += (dt + 1.0) * dn * dn;
+    by_gen += 8.0 * (dn * dn / 2.0 + (dt + 1.0) * dn);
+    cells.push_back(p);
+    return cells.back();
+  }
+  // descriptors up (returned), then generate, factor and solve under the caller's stage ids
+  const PCell* factor(int s_gen, int s_chol, int s_solve) {
+    const PCell* dc = la.put(cells);
+    const unsigned gz = (unsigned)nc, Tn = blocks(nmax, 64);
+    sg.begin(s_gen, 0.0, by_gen);
+    if (pts > 0) {
+      hipLaunchKernelGGL(k_pm_scale, dim3(blocks(pts, 256), gz), dim3(256), 0, st, dc);
+      KCHK();
+    }
+    if (nmax > 0) {
+      hipLaunchKernelGGL(k_pm_kgen, dim3(Tn, Tn, gz), dim3(256), 0, st, dc);
+      KCHK();
+      hipLaunchKernelGGL(k_pm_xgen, dim3(blocks(xel, 256), gz), dim3(256), 0, st, dc);
+      KCHK();
+    }
+    sg.end();
+    sg.begin(s_chol, fl_chol, 0.0);
+    oila::cholesky(la, st, chol);
+    sg.end();
+    sg.begin(s_solve, fl_solve, 0.0);
+    oila::trsm_right_lt(la, st, trsm);
+    sg.end();
+    return dc;
+  }
+  // after the caller's tail; the next chunk reuses the workspace and the descriptor ring
+  void finish(int32_t* status) {
+    HC(hipMemcpyAsync(status + c0, k.flag + nc, nc * 4, hipMemcpyDeviceToHost, st));
+    HC(hipStreamSynchronize(st));
+    sg.flush();
+    la.reset();
+  }
+};
 
 }  // namespace
 
@@ -283,145 +428,66 @@ extern "C" int oi_gpr_predict_multi(const double* xyt, const double* z, const in
   const oi_options o = oi_resolve(opts);
   if (int rc = oi_select_device(o)) return rc;
   return oi_guarded([&] {
-    const bool host_in = o.device_inputs == 0, want_cov = cov != nullptr;
-    hipStream_t st = (hipStream_t)o.stream;
+    const bool want_cov = cov != nullptr;
+    Front fr(o, xyt, z, offs, hyp, mean, false, kStage, S_COUNT);
     const auto [cuts, biggest] = plan_chunks(ncell, o, CHUNK_SLACK, CHUNK_CELLS, "prediction", [&](int64_t c) {
-      return cell_doubles(offs[c + 1] - offs[c], toffs[c + 1] - toffs[c], want_cov, host_in);
+      return dense_cell_doubles(offs[c + 1] - offs[c], toffs[c + 1] - toffs[c], want_cov, fr.in.host, false);
     });
     DevBuf ws((size_t)biggest * 8);
-    oila::Stager la;
-    la.bind(st);
-    StageTimer sg(kStage, S_COUNT);
-    sg.on = o.profile != 0;
-    sg.st = st;
-    std::vector<PCell> cells;
-    std::vector<oila::Chol> chol;
-    std::vector<oila::TrsmRLT> trsm;
+    hipStream_t st = fr.st;
     std::vector<oila::Gemm> syrk;
     int64_t covoff = 0;  // cell c's covariance starts at sum_{k<c} nt_k^2
     for (size_t q = 0; q + 1 < cuts.size(); ++q) {
-      const int64_t c0 = cuts[q], c1 = cuts[q + 1], nc = c1 - c0;
-      const int64_t n0 = offs[c0], nn = offs[c1] - n0, t0 = toffs[c0], tt = toffs[c1] - t0;
+      const int64_t c0 = cuts[q], c1 = cuts[q + 1], nc = c1 - c0, t0 = toffs[c0], tt = toffs[c1] - t0;
       int64_t cc = 0;
       for (int64_t c = c0; c < c1; ++c) cc += (toffs[c + 1] - toffs[c]) * (toffs[c + 1] - toffs[c]);
       Carver cv{static_cast<double*>(ws.p)};
-      const double* dx = xyt ? xyt + n0 * 3 : nullptr;
-      const double* dz = z ? z + n0 : nullptr;
-      if (host_in && nn > 0) {
-        double* hx = cv.take(nn * 3);
-        double* hz = cv.take(nn);
-        HC(hipMemcpyAsync(hx, xyt + n0 * 3, nn * 3 * 8, hipMemcpyHostToDevice, st));
-        HC(hipMemcpyAsync(hz, z + n0, nn * 8, hipMemcpyHostToDevice, st));
-        dx = hx;
-        dz = hz;
-      }
-      double* dxs = cv.take(tt * 3);
-      if (tt > 0) HC(hipMemcpyAsync(dxs, xs + t0 * 3, tt * 3 * 8, hipMemcpyHostToDevice, st));
-      double* dfs = cv.take(tt);
-      double* dsd = cv.take(tt);
-      double* dlz = cv.take(nc);
-      int32_t* dflag = reinterpret_cast<int32_t*>(cv.take(nc));  // info [nc], status [nc]
-      double* dcov = want_cov ? cv.take(cc) : nullptr;
-      HC(hipMemsetAsync(dflag, 0, nc * 8, st));
-      cells.clear();
-      chol.clear();
-      trsm.clear();
+      fr.begin(cv, c0, c1, xs + t0 * 3, tt, want_cov ? cc : -1);
+      const DenseChunk& k = fr.k;
       syrk.clear();
-      int64_t nmax = 0, ntmax = 0, pts = 0, xel = 0, co = 0;
-      double fl_chol = 0.0, fl_solve = 0.0, fl_cov = 0.0, by_gen = 0.0, by_red = 0.0;
+      int64_t co = 0;
+      double fl_cov = 0.0, by_red = 0.0;
       for (int64_t c = c0; c < c1; ++c) {
-        const int64_t n = offs[c + 1] - offs[c], nt = toffs[c + 1] - toffs[c], Np = up(n, 64);
-        const double* h = hyp + c * 5;
-        PCell p;
-        p.x = dx ? dx + (offs[c] - n0) * 3 : nullptr;
-        p.z = dz ? dz + (offs[c] - n0) : nullptr;
-        p.xs = dxs + (toffs[c] - t0) * 3;
-        p.sc = cv.take(3 * n);
-        p.xsc = cv.take(3 * nt);
-        p.K = cv.take(Np * Np);
-        double* dinv = cv.take(Np * 64);
-        p.X = cv.take((nt + 1) * n);
-        p.cov = want_cov ? dcov + co : nullptr;
-        p.fs = dfs + (toffs[c] - t0);
-        p.sd = dsd + (toffs[c] - t0);
-        p.lz = dlz + (c - c0);
-        p.info = dflag + (c - c0);
-        p.status = dflag + nc + (c - c0);
-        p.n = (int)n;
-        p.nt = (int)nt;
-        p.Np = (int)Np;
-        p.l0 = h[0];
-        p.l1 = h[1];
-        p.l2 = h[2];
-        p.sf2 = h[3];
-        p.sn2 = h[4];
-        p.mean = mean;
-        cells.push_back(p);
-        if (n > 0) {
-          chol.push_back(oila::Chol{p.K, dinv, p.info, p.Np, p.Np});
-          trsm.push_back(oila::TrsmRLT{p.X, p.K, dinv, p.nt + 1, p.n, p.nt + 1, p.Np});
-        }
+        const int64_t nt = toffs[c + 1] - toffs[c];
+        DenseCell a;
+        PCell& p = fr.add(cv, c, nt, a);
+        p.xs = k.xs + (toffs[c] - t0) * 3;
+        p.xsc = a.xsc;
+        p.cov = want_cov ? k.cov + co : nullptr;
+        p.fs = k.mu + (toffs[c] - t0);
+        p.sd = k.sd + (toffs[c] - t0);
+        p.lz = k.lz + (c - c0);
         if (want_cov && nt > 0)  // cov <- Kxs - X[:nt] X[:nt]' on the lower tiles
           syrk.push_back(oila::Gemm{p.X, p.X, p.cov, p.nt, p.nt, p.n, p.nt + 1, p.nt + 1, p.nt, -1.0, 1.0, 1});
         co += nt * nt;
-        nmax = std::max(nmax, n);
-        ntmax = std::max(ntmax, nt);
-        pts = std::max(pts, n + nt);
-        xel = std::max(xel, (nt + 1) * n);
-        const double dn = (double)n, dt = (double)nt;
-        fl_chol += dn * dn * dn / 3.0;
-        fl_solve += (dt + 1.0) * dn * dn;
+        const double dn = (double)p.n, dt = (double)nt;
         fl_cov += dt * dt * dn;
-        by_gen += 8.0 * (dn * dn / 2.0 + (dt + 1.0) * dn);
         by_red += 8.0 * (dt + 1.0) * dn;
       }
       if (cv.off > biggest) throw HipErr{"oi_gpr_predict_multi: workspace layout exceeds its estimate"};
-      const PCell* dc = la.put(cells);
-      const unsigned gz = (unsigned)nc;
-      const unsigned Tn = blocks(nmax, 64), Tt = blocks(ntmax, 64);
-      sg.begin(S_GEN, 0.0, by_gen);
-      if (pts > 0) {
-        hipLaunchKernelGGL(k_pm_scale, dim3(blocks(pts, 256), gz), dim3(256), 0, st, dc);
-        KCHK();
-      }
-      if (nmax > 0) {
-        hipLaunchKernelGGL(k_pm_kgen, dim3(Tn, Tn, gz), dim3(256), 0, st, dc);
-        KCHK();
-        hipLaunchKernelGGL(k_pm_xgen, dim3(blocks(xel, 256), gz), dim3(256), 0, st, dc);
-        KCHK();
-      }
-      sg.end();
-      sg.begin(S_CHOL, fl_chol, 0.0);
-      oila::cholesky(la, st, chol);
-      sg.end();
-      sg.begin(S_SOLVE, fl_solve, 0.0);
-      oila::trsm_right_lt(la, st, trsm);
-      sg.end();
-      sg.begin(S_REDUCE, by_red / 2.0, by_red);
-      hipLaunchKernelGGL(k_pm_reduce, dim3(blocks(ntmax + 1, 64), gz), dim3(256), 0, st, dc);
+      const PCell* dc = fr.factor(S_GEN, S_CHOL, S_SOLVE);
+      const unsigned gz = (unsigned)nc, Tt = blocks(fr.ntmax, 64);
+      fr.sg.begin(S_REDUCE, by_red / 2.0, by_red);
+      hipLaunchKernelGGL(k_pm_reduce, dim3(blocks(fr.ntmax + 1, 64), gz), dim3(256), 0, st, dc);
       KCHK();
-      sg.end();
-      if (want_cov && ntmax > 0) {
-        sg.begin(S_COV, fl_cov, 8.0 * (double)cc);
+      fr.sg.end();
+      if (want_cov && fr.ntmax > 0) {
+        fr.sg.begin(S_COV, fl_cov, 8.0 * (double)cc);
         hipLaunchKernelGGL(k_pm_kxs, dim3(Tt, Tt, gz), dim3(256), 0, st, dc);
         KCHK();
-        oila::gemm(la, st, false, true, syrk);
+        oila::gemm(fr.la, st, false, true, syrk);
         hipLaunchKernelGGL(k_pm_mirror, dim3(Tt, Tt, gz), dim3(256), 0, st, dc);
         KCHK();
-        sg.end();
+        fr.sg.end();
       }
       if (tt > 0) {
-        HC(hipMemcpyAsync(fs + t0, dfs, tt * 8, hipMemcpyDeviceToHost, st));
-        HC(hipMemcpyAsync(sd + t0, dsd, tt * 8, hipMemcpyDeviceToHost, st));
+        HC(hipMemcpyAsync(fs + t0, k.mu, tt * 8, hipMemcpyDeviceToHost, st));
+        HC(hipMemcpyAsync(sd + t0, k.sd, tt * 8, hipMemcpyDeviceToHost, st));
       }
-      if (lz) HC(hipMemcpyAsync(lz + c0, dlz, nc * 8, hipMemcpyDeviceToHost, st));
-      HC(hipMemcpyAsync(status + c0, dflag + nc, nc * 4, hipMemcpyDeviceToHost, st));
-      if (want_cov && cc > 0) HC(hipMemcpyAsync(cov + covoff, dcov, cc * 8, hipMemcpyDeviceToHost, st));
+      if (lz) HC(hipMemcpyAsync(lz + c0, k.lz, nc * 8, hipMemcpyDeviceToHost, st));
+      if (want_cov && cc > 0) HC(hipMemcpyAsync(cov + covoff, k.cov, cc * 8, hipMemcpyDeviceToHost, st));
       covoff += cc;
-      // the next chunk reuses the workspace and the descriptor ring
-      HC(hipStreamSynchronize(st));
-      sg.flush();
-      la.reset();
+      fr.finish(status);
     }
     return 0;
   });
@@ -652,15 +718,6 @@ __global__ void __launch_bounds__(256) k_loo_finish(const LCell* __restrict__ cs
 enum { L_GEN, L_CHOL, L_SOLVE, L_SWEEP, L_COUNT };
 const char* kLooStage[L_COUNT] = {"loo_generate", "loo_cholesky", "loo_solve", "loo_sweep"};
 
-// Workspace of one cell in doubles: scaled inputs 3 n, K Np^2 (L below, the
-// panels of W' above the diagonal blocks -- the sweep needs no n x n array of
-// its own), the diagonal-block inverses and their transposes 2 x 64 Np, zt n,
-// lpl partials Np / 64, mu + sd 2 n, inputs 4 n (host inputs only), lpl + flags 2
-int64_t loo_cell_doubles(int64_t n, bool host_inputs) {
-  const int64_t Np = up(n, 64);
-  return up(3 * n, 32) + Np * Np + 2 * Np * 64 + up(n, 32) + up(Np / 64, 32) + 2 * n + (host_inputs ? 4 * n : 0) + 2;
-}
-
 }  // namespace
 
 extern "C" int oi_gpr_loo(const double* xyt, const double* z, const int64_t* offs, int64_t ncell,
@@ -681,84 +738,27 @@ extern "C" int oi_gpr_loo(const double* xyt, const double* z, const int64_t* off
   const oi_options o = oi_resolve(opts);
   if (int rc = oi_select_device(o)) return rc;
   return oi_guarded([&] {
-    const bool host_in = o.device_inputs == 0;
-    hipStream_t st = (hipStream_t)o.stream;
+    Front fr(o, xyt, z, offs, hyp, mean, true, kLooStage, L_COUNT);
     const auto [cuts, biggest] = plan_chunks(ncell, o, CHUNK_SLACK, CHUNK_CELLS, "leave-one-out", [&](int64_t c) {
-      return loo_cell_doubles(offs[c + 1] - offs[c], host_in);
+      return dense_cell_doubles(offs[c + 1] - offs[c], 0, false, fr.in.host, true);
     });
     DevBuf ws((size_t)biggest * 8);
-    oila::Stager la;
-    la.bind(st);
-    StageTimer sg(kLooStage, L_COUNT);
-    sg.on = o.profile != 0;
-    sg.st = st;
-    std::vector<PCell> cells;
+    hipStream_t st = fr.st;
     std::vector<LCell> lcells;
     std::vector<LItem> items;
-    std::vector<oila::Chol> chol;
-    std::vector<oila::TrsmRLT> trsm;
     for (size_t q = 0; q + 1 < cuts.size(); ++q) {
-      const int64_t c0 = cuts[q], c1 = cuts[q + 1], nc = c1 - c0;
-      const int64_t n0 = offs[c0], nn = offs[c1] - n0;
+      const int64_t c0 = cuts[q], c1 = cuts[q + 1], nc = c1 - c0, n0 = offs[c0], nn = offs[c1] - n0;
       Carver cv{static_cast<double*>(ws.p)};
-      const double* dx = xyt ? xyt + n0 * 3 : nullptr;
-      const double* dz = z ? z + n0 : nullptr;
-      if (host_in && nn > 0) {
-        double* hx = cv.take(nn * 3);
-        double* hz = cv.take(nn);
-        HC(hipMemcpyAsync(hx, xyt + n0 * 3, nn * 3 * 8, hipMemcpyHostToDevice, st));
-        HC(hipMemcpyAsync(hz, z + n0, nn * 8, hipMemcpyHostToDevice, st));
-        dx = hx;
-        dz = hz;
-      }
-      double* dmu = cv.take(nn);
-      double* dsd = cv.take(nn);
-      double* dlpl = cv.take(nc);
-      int32_t* dflag = reinterpret_cast<int32_t*>(cv.take(nc));  // info [nc], status [nc]
-      HC(hipMemsetAsync(dflag, 0, nc * 8, st));
-      cells.clear();
+      fr.begin(cv, c0, c1, nullptr, 0, -1);
+      const DenseChunk& k = fr.k;
       lcells.clear();
       items.clear();
-      chol.clear();
-      trsm.clear();
-      int64_t nmax = 0;
-      double fl = 0.0, fl_solve = 0.0, by_gen = 0.0;
       for (int64_t c = c0; c < c1; ++c) {
-        const int64_t n = offs[c + 1] - offs[c], Np = up(n, 64);
-        const double* h = hyp + c * 5;
-        PCell p{};
-        p.x = dx ? dx + (offs[c] - n0) * 3 : nullptr;
-        p.z = dz ? dz + (offs[c] - n0) : nullptr;
-        p.sc = cv.take(3 * n);
-        p.K = cv.take(Np * Np);
-        double* dinv = cv.take(Np * 64);
-        double* wdt = cv.take(Np * 64);
-        p.X = cv.take(n);  // nt = 0: the one row z - mean, then zt
-        double* part = cv.take(Np / 64);
-        p.info = dflag + (c - c0);
-        p.status = dflag + nc + (c - c0);
-        p.n = (int)n;
-        p.nt = 0;
-        p.Np = (int)Np;
-        p.l0 = h[0];
-        p.l1 = h[1];
-        p.l2 = h[2];
-        p.sf2 = h[3];
-        p.sn2 = h[4];
-        p.mean = mean;
-        cells.push_back(p);
-        lcells.push_back(LCell{p.K, dinv, wdt, p.X, p.z, dmu + (offs[c] - n0), dsd + (offs[c] - n0), part,
-                               dlpl + (c - c0), p.info, p.status, p.n, p.Np});
-        if (n > 0) {
-          chol.push_back(oila::Chol{p.K, dinv, p.info, p.Np, p.Np});
-          trsm.push_back(oila::TrsmRLT{p.X, p.K, dinv, 1, p.n, 1, p.Np});
-        }
-        for (int j = 0; j < (int)(Np / 64); ++j) items.push_back(LItem{(int)(c - c0), j});
-        nmax = std::max(nmax, n);
-        const double dn = (double)n;
-        fl += dn * dn * dn / 3.0;
-        fl_solve += dn * dn;
-        by_gen += 8.0 * (dn * dn / 2.0 + dn);
+        DenseCell a;
+        const PCell& p = fr.add(cv, c, 0, a);
+        lcells.push_back(LCell{p.K, a.dinv, a.wdt, p.X, p.z, k.mu + (offs[c] - n0), k.sd + (offs[c] - n0), a.part,
+                               k.lz + (c - c0), p.info, p.status, p.n, p.Np});
+        for (int j = 0; j < p.Np / 64; ++j) items.push_back(LItem{(int)(c - c0), j});
       }
       if (cv.off > biggest) throw HipErr{"oi_gpr_loo: workspace layout exceeds its estimate"};
       // the longest block columns first (j ascending: Np / 64 - j tiles each);
@@ -766,45 +766,38 @@ extern "C" int oi_gpr_loo(const double* xyt, const double* z, const int64_t* off
       std::stable_sort(items.begin(), items.end(), [&](const LItem& a, const LItem& b) {
         return lcells[a.cell].Np / 64 - a.j > lcells[b.cell].Np / 64 - b.j;
       });
-      const PCell* dc = la.put(cells);
-      const LCell* dl = la.put(lcells);
-      const unsigned gz = (unsigned)nc, Tn = blocks(nmax, 64);
-      sg.begin(L_GEN, 0.0, by_gen);
-      if (nmax > 0) {
-        hipLaunchKernelGGL(k_pm_scale, dim3(blocks(nmax, 256), gz), dim3(256), 0, st, dc);
-        KCHK();
-        hipLaunchKernelGGL(k_pm_kgen, dim3(Tn, Tn, gz), dim3(256), 0, st, dc);
-        KCHK();
-        hipLaunchKernelGGL(k_pm_xgen, dim3(blocks(nmax, 256), gz), dim3(256), 0, st, dc);
-        KCHK();
-      }
-      sg.end();
-      sg.begin(L_CHOL, fl, 0.0);
-      oila::cholesky(la, st, chol);
-      sg.end();
-      sg.begin(L_SOLVE, fl_solve, 0.0);
-      oila::trsm_right_lt(la, st, trsm);
-      sg.end();
-      sg.begin(L_SWEEP, fl, 0.0);
+      const LCell* dl = fr.la.put(lcells);
+      fr.factor(L_GEN, L_CHOL, L_SOLVE);
+      fr.sg.begin(L_SWEEP, fr.fl_chol, 0.0);
       if (!items.empty()) {
-        const LItem* di = la.put(items);
+        const LItem* di = fr.la.put(items);
         hipLaunchKernelGGL(k_loo_sweep, dim3((unsigned)items.size()), dim3(256), 0, st, dl, di);
         KCHK();
       }
       hipLaunchKernelGGL(k_loo_finish, dim3(blocks(nc, 256)), dim3(256), 0, st, dl, (int)nc);
       KCHK();
-      sg.end();
+      fr.sg.end();
       if (nn > 0) {
-        HC(hipMemcpyAsync(mu + n0, dmu, nn * 8, hipMemcpyDeviceToHost, st));
-        HC(hipMemcpyAsync(sd + n0, dsd, nn * 8, hipMemcpyDeviceToHost, st));
+        HC(hipMemcpyAsync(mu + n0, k.mu, nn * 8, hipMemcpyDeviceToHost, st));
+        HC(hipMemcpyAsync(sd + n0, k.sd, nn * 8, hipMemcpyDeviceToHost, st));
       }
-      if (lpl) HC(hipMemcpyAsync(lpl + c0, dlpl, nc * 8, hipMemcpyDeviceToHost, st));
-      HC(hipMemcpyAsync(status + c0, dflag + nc, nc * 4, hipMemcpyDeviceToHost, st));
-      // the next chunk reuses the workspace and the descriptor ring
-      HC(hipStreamSynchronize(st));
-      sg.flush();
-      la.reset();
+      if (lpl) HC(hipMemcpyAsync(lpl + c0, k.lz, nc * 8, hipMemcpyDeviceToHost, st));
+      fr.finish(status);
     }
     return 0;
   });
+}
+
+// Test hook (not in oi.h): what the chunk planner counts for one cell of path
+// 0 oi_gpr_predict_multi, 1 oi_gpr_loo, 2 oi_svgp_predict / oi_svgp_elbo,
+// 3 oi_nystrom_predict_multi; flags 1 cov, 2 host inputs, 4 ELBO; -1: no such path
+extern "C" int64_t oi_test_cell_doubles(int32_t path, int64_t n, int64_t nt, int64_t M, int32_t flags) {
+  const bool cov = flags & 1, host = flags & 2, elbo = flags & 4;
+  switch (path) {
+    case 0: return dense_cell_doubles(n, nt, cov, host, false);
+    case 1: return dense_cell_doubles(n, 0, false, host, true);
+    case 2: return oi_svgp_cell_doubles((int)M, n, cov, host, elbo);
+    case 3: return oi_nystrom_multi_cell_doubles(n, M, nt, cov);
+  }
+  return -1;
 }

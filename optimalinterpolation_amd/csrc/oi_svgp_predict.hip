@@ -319,15 +319,52 @@ struct Job {
   int32_t* status;
 };
 
-// workspace of one cell in doubles (the chunk-wide arrays are the cells' parts
-// back to back, so their share is not rounded): record, parameter row, status,
-// then the staged host inputs, the outputs and (cov) the two M x n panels and
-// the n x n matrix, or (ELBO) the block partials
+// A chunk's workspace, described once (nc cells from c0, tt rows from row t0,
+// pp covariance elements / ELBO partials): parameter rows, records, status,
+// the staged host inputs, the outputs and (cov) the two M x tt panels and the
+// covariances, or (ELBO) the block partials.  All chunk-wide, the cells' parts
+// back to back: a cell's size for the chunk planner is this layout for the
+// cell alone on a counting Carver that does not round.
+struct SpArrays {
+  double *par, *rec;
+  int32_t* stat;
+  const double *pts, *y;  // the caller's device arrays (pbase 0) or the chunk's staged rows (pbase t0)
+  int64_t pbase;
+  double *mean, *var, *A, *SA, *cov, *part, *elbo;
+};
+SpArrays sp_layout(Carver& cv, const Job& j, bool host_in, hipStream_t st, int64_t c0, int64_t nc, int64_t t0,
+                   int64_t tt, int64_t pp) {
+  const int P = oi_svgp_param_count(j.M);
+  SpArrays a{};
+  a.par = stage_host(cv, j.params + c0 * P, nc * P, st);
+  a.rec = cv.take(nc * rec_doubles(j.M));
+  a.stat = reinterpret_cast<int32_t*>(cv.take(nc));
+  a.pts = j.pts;
+  a.y = j.y;
+  if (host_in) {
+    a.pts = stage_host(cv, j.pts + t0 * 3, tt * 3, st);
+    a.pbase = t0;
+    if (j.elbo) a.y = stage_host(cv, j.y + t0, tt, st);
+  }
+  if (j.elbo) {
+    a.part = cv.take(pp);
+    a.elbo = cv.take(nc);
+  } else {
+    a.mean = cv.take(tt);
+    a.var = cv.take(tt);
+    if (j.cov) {
+      a.A = cv.take(j.M * tt);
+      a.SA = cv.take(j.M * tt);
+      a.cov = cv.take(pp);
+    }
+  }
+  return a;
+}
+int64_t cell_pp(const Job& j, int64_t n) { return j.elbo ? (int64_t)blocks(n, TL) : n * n; }
 int64_t cell_doubles(const Job& j, int64_t n, bool host_in) {
-  int64_t d = rec_doubles(j.M) + oi_svgp_param_count(j.M) + 1;
-  if (host_in) d += 3 * n + (j.elbo ? n : 0);
-  if (j.elbo) return d + blocks(n, TL) + 1;
-  return d + 2 * n + (j.cov ? 2 * j.M * n + n * n : 0);
+  Carver cv{nullptr, 0, 1};
+  sp_layout(cv, j, host_in, nullptr, 0, 1, 0, n, cell_pp(j, n));
+  return cv.off;
 }
 
 int run(const Job& j, const oi_options& o) {
@@ -347,7 +384,7 @@ int run(const Job& j, const oi_options& o) {
   std::vector<int64_t> pre(ncell + 1, 0);
   for (int64_t c = 0; c < ncell; ++c) {
     const int64_t n = j.offs[c + 1] - j.offs[c];
-    pre[c + 1] = pre[c] + (elbo ? (int64_t)blocks(n, TL) : n * n);
+    pre[c + 1] = pre[c] + cell_pp(j, n);
   }
   DevBuf ws((size_t)biggest * 8), doffs((ncell + 1) * 8), dpre((ncell + 1) * 8);
   HC(hipMemcpyAsync(doffs.p, j.offs, (ncell + 1) * 8, hipMemcpyHostToDevice, st));
@@ -361,71 +398,43 @@ int run(const Job& j, const oi_options& o) {
     int64_t nmax = 0;
     for (int64_t c = c0; c < c1; ++c) nmax = std::max(nmax, j.offs[c + 1] - j.offs[c]);
     Carver cv{static_cast<double*>(ws.p)};
-    double* dpar = cv.take(nc * P);
-    double* drec = cv.take(nc * RD);
-    int32_t* dstat = reinterpret_cast<int32_t*>(cv.take(nc));
-    SpChunk k{drec, j.pts, j.y, doffs.as<int64_t>(), c0, 0, t0, M};
-    if (host_in) {
-      double* hp = cv.take(tt * 3);
-      if (tt > 0) HC(hipMemcpyAsync(hp, j.pts + t0 * 3, tt * 3 * 8, hipMemcpyHostToDevice, st));
-      k.pts = hp;
-      k.pbase = t0;
-      if (elbo) {
-        double* hy = cv.take(tt);
-        HC(hipMemcpyAsync(hy, j.y + t0, tt * 8, hipMemcpyHostToDevice, st));
-        k.y = hy;
-      }
-    }
-    double *dmean = nullptr, *dvar = nullptr, *dA = nullptr, *dSA = nullptr, *dcov = nullptr;
-    double *dpart = nullptr, *delbo = nullptr;
-    if (elbo) {
-      dpart = cv.take(pp);
-      delbo = cv.take(nc);
-    } else {
-      dmean = cv.take(tt);
-      dvar = cv.take(tt);
-      if (want_cov) {
-        dA = cv.take(M * tt);
-        dSA = cv.take(M * tt);
-        dcov = cv.take(pp);
-      }
-    }
+    const SpArrays a = sp_layout(cv, j, host_in, st, c0, nc, t0, tt, pp);
     if (cv.off > biggest) throw HipErr{"svgp predict: workspace layout exceeds its estimate"};
-    HC(hipMemcpyAsync(dpar, j.params + c0 * P, nc * P * 8, hipMemcpyHostToDevice, st));
+    const SpChunk k{a.rec, a.pts, a.y, doffs.as<int64_t>(), c0, a.pbase, t0, M};
     const double dM = M, dT = (double)tt;
     sg.begin(S_MODEL, (double)nc * dM * dM * dM / 3.0, 8.0 * (double)nc * (P + RD));
-    hipLaunchKernelGGL(k_sp_model, dim3((unsigned)nc), dim3(256), model_lds(M), st, dpar, M, P, drec, dstat);
+    hipLaunchKernelGGL(k_sp_model, dim3((unsigned)nc), dim3(256), model_lds(M), st, a.par, M, P, a.rec, a.stat);
     KCHK();
     sg.end();
     if (nmax > 0) {
       // per target: the substitution M^2, S'a M^2, k_u and the dot products
       sg.begin(S_TARGETS, dT * (2.0 * dM * dM + 30.0 * dM), 8.0 * dT * (5.0 + (want_cov ? 2.0 * dM : 0.0)));
       hipLaunchKernelGGL(k_sp_targets, dim3(blocks(nmax, TL), (unsigned)nc), dim3(TL), targets_lds(M), st, k,
-                         j.with_noise, dmean, dvar, dA, dSA, dpart, dpre.as<int64_t>());
+                         j.with_noise, a.mean, a.var, a.A, a.SA, a.part, dpre.as<int64_t>());
       KCHK();
       sg.end();
     }
     if (want_cov && nmax > 0) {
       const unsigned T = blocks(nmax, CT);
       sg.begin(S_COV, 4.0 * dM * (double)pp, 8.0 * (double)pp);
-      hipLaunchKernelGGL(k_sp_cov, dim3(T * T, (unsigned)nc), dim3(256), cov_lds(M), st, k, dA, dSA, dvar, dcov,
+      hipLaunchKernelGGL(k_sp_cov, dim3(T * T, (unsigned)nc), dim3(256), cov_lds(M), st, k, a.A, a.SA, a.var, a.cov,
                          dpre.as<int64_t>());
       KCHK();
       sg.end();
     }
     if (elbo) {
       sg.begin(S_REDUCE, (double)pp, 8.0 * (double)pp);
-      hipLaunchKernelGGL(k_sp_reduce, dim3((unsigned)nc), dim3(64), 0, st, drec, M, dpart, dpre.as<int64_t>(), c0,
-                         delbo);
+      hipLaunchKernelGGL(k_sp_reduce, dim3((unsigned)nc), dim3(64), 0, st, a.rec, M, a.part, dpre.as<int64_t>(), c0,
+                         a.elbo);
       KCHK();
       sg.end();
-      HC(hipMemcpyAsync(j.elbo + c0, delbo, nc * 8, hipMemcpyDeviceToHost, st));
+      HC(hipMemcpyAsync(j.elbo + c0, a.elbo, nc * 8, hipMemcpyDeviceToHost, st));
     } else if (tt > 0) {
-      HC(hipMemcpyAsync(j.mean + t0, dmean, tt * 8, hipMemcpyDeviceToHost, st));
-      HC(hipMemcpyAsync(j.var + t0, dvar, tt * 8, hipMemcpyDeviceToHost, st));
-      if (want_cov && pp > 0) HC(hipMemcpyAsync(j.cov + pre[c0], dcov, pp * 8, hipMemcpyDeviceToHost, st));
+      HC(hipMemcpyAsync(j.mean + t0, a.mean, tt * 8, hipMemcpyDeviceToHost, st));
+      HC(hipMemcpyAsync(j.var + t0, a.var, tt * 8, hipMemcpyDeviceToHost, st));
+      if (want_cov && pp > 0) HC(hipMemcpyAsync(j.cov + pre[c0], a.cov, pp * 8, hipMemcpyDeviceToHost, st));
     }
-    HC(hipMemcpyAsync(j.status + c0, dstat, nc * 4, hipMemcpyDeviceToHost, st));
+    HC(hipMemcpyAsync(j.status + c0, a.stat, nc * 4, hipMemcpyDeviceToHost, st));
     // the next chunk reuses the workspace
     HC(hipStreamSynchronize(st));
     sg.flush();
@@ -434,6 +443,11 @@ int run(const Job& j, const oi_options& o) {
 }
 
 }  // namespace
+
+int64_t oi_svgp_cell_doubles(int M, int64_t n, bool cov, bool host_inputs, bool elbo) {
+  double set;  // of a Job's outputs, the layout asks only which are set
+  return cell_doubles(Job{.M = M, .cov = cov ? &set : nullptr, .elbo = elbo ? &set : nullptr}, n, host_inputs);
+}
 
 extern "C" int oi_svgp_predict(const double* params, int32_t M, int64_t ncell, const double* xs,
                                const int64_t* toffs, int32_t with_noise, double* mean, double* var,

@@ -19,6 +19,7 @@ from conftest import load_golden
 from oracle import gp_oracle as O
 from optimalinterpolation_amd import _lib, gpr, nystrom, synthetic
 import loo_ref as R
+import workspace_ref as W
 
 pytestmark = pytest.mark.gpu
 
@@ -119,8 +120,9 @@ def test_batch_equals_single(edge, edge_hyp, edge_result):
 
 
 def test_chunking_is_bitwise_neutral(edge, edge_hyp, edge_result):
-    # the first ten cells (n <= 333): the largest needs 200 016 doubles and all
-    # of them 477 000, so 1.6 MiB (209 715 doubles) cuts after n = 128 and n = 130
+    # the first ten cells (n <= 333), sized by the library's own count
+    # (workspace_ref.cell_doubles; tests/test_workspace_layout.py pins the
+    # largest): 1.6 MiB (209 715 doubles) cuts after n = 128 and n = 130
     k = 10
     e = edge.offs[k]
     _lib.profile_reset()
@@ -169,8 +171,21 @@ def test_failed_cell_is_nan_and_mates_unchanged(edge, edge_hyp, edge_result):
 
 def test_cell_larger_than_the_pool_is_nomem(edge, edge_hyp):
     with pytest.raises(_lib.OiError, match=r'error -3.*pool_bytes'):
-        # the n = 1100 cell alone needs ~11.9 MB
+        # the n = 1100 cell alone (workspace_ref.cell_doubles(W.LOO, 1100) doubles) needs ~11.9 MB
         _lib.gpr_loo(edge.xyt, edge.z, edge.offs, edge.mean, edge_hyp, pool_bytes=4 << 20)
+
+
+def test_pool_that_fits_the_largest_cell_exactly():
+    """A pool of exactly the planner's count for the larger cell (plus the
+    chunk's slack) holds the call, one cell per chunk; one double less does not."""
+    cells = synthetic.make_cells([65, 1], seed=12)
+    hyp = np.tile(HYP, (2, 1))
+    free = _lib.gpr_loo(cells.xyt, cells.z, cells.offs, cells.mean, hyp)
+    fit = 8 * (W.SLACK[W.LOO] + W.cell_doubles(W.LOO, 65))
+    assert not free[3].any()
+    assert _same(_lib.gpr_loo(cells.xyt, cells.z, cells.offs, cells.mean, hyp, pool_bytes=fit), free)
+    with pytest.raises(_lib.OiError, match=r"error -3: a cell's leave-one-out workspace does not fit pool_bytes"):
+        _lib.gpr_loo(cells.xyt, cells.z, cells.offs, cells.mean, hyp, pool_bytes=fit - 8)
 
 
 def test_empty_cell_and_single_observation(edge, edge_hyp, edge_result):

@@ -18,6 +18,7 @@ import pytest
 from conftest import load_golden
 from oracle import gp_oracle as O
 from optimalinterpolation_amd import _lib, gpr, nystrom, synthetic
+import workspace_ref as W
 
 pytestmark = pytest.mark.gpu
 
@@ -168,7 +169,25 @@ def test_chunking_is_bitwise_neutral(edge_batch, edge_result):
 
 def test_cell_larger_than_the_pool_is_nomem(edge_batch):
     with pytest.raises(_lib.OiError, match=r'error -3.*pool_bytes'):
-        edge_batch.run(pool_bytes=256 * 1024)  # the n = 200 cell alone needs ~0.65 MiB
+        # the n = 200 cell alone (workspace_ref.cell_doubles(W.PREDICT, 200, 0, cov=True) doubles) needs ~0.65 MiB
+        edge_batch.run(pool_bytes=256 * 1024)
+
+
+def test_pool_that_fits_the_largest_cell_exactly():
+    """A pool of exactly the planner's count for the larger cell (plus the
+    chunk's slack) holds the call, one cell per chunk; one double less does not."""
+    d = load_golden('predict64.npz')
+    cells = []
+    for c, n in enumerate((65, 1)):
+        a = d['offs'][c]
+        cells.append((d['x'][a:a + n], d['y'][a:a + n], _lattice(d['xs'][c], n), d['hyp'][c]))
+    b = Batch(cells, float(d['mean']))
+    free = b.run()
+    fit = 8 * (W.SLACK[W.PREDICT] + W.cell_doubles(W.PREDICT, 65, 65, cov=True))
+    assert not free[4].any()
+    assert _same(b.run(pool_bytes=fit), free)
+    with pytest.raises(_lib.OiError, match=r"error -3: a cell's prediction workspace does not fit pool_bytes"):
+        b.run(pool_bytes=fit - 8)
 
 
 def test_failed_cell_is_nan_and_mates_unchanged(edge_batch, edge_result):

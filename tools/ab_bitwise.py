@@ -8,11 +8,14 @@ must not change a single bit).  One small case per entry family:
                 in n and M
   prediction    gpr_predict_multi with the covariance, n and nt around the
                 64-tile, in one chunk and in several
+  leave-one-out gpr_loo with lpl, n around the 64-tile, in one chunk and in several
+  Nystrom multi nystrom_predict_multi without and with the covariance, n, M and
+                nt around the 64-tile
   SVGP          a short Adam run with logging; predict_f with the covariance
                 and the ELBO at its parameters, in one chunk and in several
   device inputs the Nystrom fit and the SVGP run again on device tensors
   day helpers   smooth_fields, ball query + gather
-  profile       stage names and launch counts of the two staged paths; the main
+  profile       stage names and launch counts of the staged paths; the main
                 engine's kernels with their launch counts and counted flops
 Usage (GPU box):
     python tools/ab_bitwise.py run OUT.npz        # with OI_LIB set as wanted
@@ -111,6 +114,44 @@ def _predict(_lib, synthetic):
                 pm_cov2=cov2, pm_st2=st2, pm_stage_names=names, pm_stage_launches=launches)
 
 
+def _loo(_lib, synthetic):
+    ns = [1, 63, 64, 65, 128, 130, 333]
+    c = synthetic.make_cells(ns, seed=13)
+    hyp = np.tile(synthetic.FIXED_HYPERS, (len(ns), 1))
+    args = (c.xyt, c.z, c.offs, c.mean, hyp)
+    mu, sd, lpl, st = _lib.gpr_loo(*args)
+    # 1.6 MiB (209 715 doubles) holds the n = 333 cell but not it and its neighbours: >= 2 chunks
+    mu2, sd2, lpl2, st2 = _lib.gpr_loo(*args, pool_bytes=1677721)
+    _lib.profile_reset()
+    _lib.gpr_loo(*args, pool_bytes=1677721, profile=True)
+    names, launches = _stages(_lib, 'loo_')
+    assert launches.max() >= 2, "pool_bytes did not force a second chunk"
+    return dict(loo_mu=mu, loo_sd=sd, loo_lpl=lpl, loo_st=st, loo_mu2=mu2, loo_sd2=sd2, loo_lpl2=lpl2, loo_st2=st2,
+                loo_stage_names=names, loo_stage_launches=launches)
+
+
+def _nystrom_multi(_lib, synthetic):
+    from optimalinterpolation_amd import nystrom
+    ns, Ms, nts = [70, 130, 200, 260], np.array([20, 33, 64, 65]), [1, 64, 65, 130]
+    c = synthetic.make_cells(ns, seed=14)
+    sel, soffs = nystrom._ragged_sel(c.offs, Ms)
+    hyp = np.tile(synthetic.FIXED_HYPERS, (len(ns), 1))
+    rng = np.random.default_rng(15)
+    toffs = np.concatenate([[0], np.cumsum(nts)])
+    xs = np.repeat(c.xs, nts, axis=0) + rng.normal(0, 1.0, (toffs[-1], 3)) * [5e4, 5e4, 1.0]
+    args = (c.xyt, c.z - c.mean, c.offs, sel, soffs, hyp, xs, toffs)
+    r = {}
+    for tag, cov in (('', False), ('_cov', True)):
+        _lib.profile_reset()
+        fs, sd, cv, st = _lib.nystrom_predict_multi(*args, mean=c.mean, cov=cov, profile=True)
+        names, launches = _stages(_lib, 'nys_')
+        r.update({f'nysm_fs{tag}': fs, f'nysm_sd{tag}': sd, f'nysm_st{tag}': st, f'nysm_stage_names{tag}': names,
+                  f'nysm_stage_launches{tag}': launches})
+    r['nysm_cov'] = cv
+    _lib.profile_reset()
+    return r
+
+
 def _svgp(_lib):
     rng = np.random.default_rng(11)
     n, M, nc = 90, 8, 2
@@ -165,6 +206,8 @@ def run(out):
     r = _engine(_lib, synthetic)
     r.update(_nystrom(_lib, synthetic))
     r.update(_predict(_lib, synthetic))
+    r.update(_loo(_lib, synthetic))
+    r.update(_nystrom_multi(_lib, synthetic))
     r.update(_svgp(_lib))
     r.update(_day(_lib))
     np.savez(out, **r)
