@@ -162,8 +162,16 @@ int oi_nlml_grad_batch(const double* xyt, const double* y, const double* mX,
  *   fields [nf x ny x nx]  (the reference's 2-D grids, row-major)
  *   vmax   [nf]            clip values (GPR:303-307: 2*radius*1000, .., T, 0.1, 0.05)
  *   mask   [ny x nx]       SIE grid; NaN entries are set to NaN in the output
- *   kern   [ks x ks] or NULL: the Gaussian2DKernel(x_stddev=std) array; NULL =>
- *                          built here from std (astropy's definition)
+ *   kern   [ks x ks] or NULL: the Gaussian2DKernel(x_stddev=std) array, ks odd,
+ *                          <= 65 (std is then ignored).  NULL => built here from
+ *                          std in (0, 8] by astropy's definition, normalised by a
+ *                          sum taken in numpy's order (arr.sum()): every entry is
+ *                          within 4 ulp of numpy's array (libm's exp against
+ *                          numpy's; bit-equal at std = 1 where the two agree).
+ *                          The smoothing is bit-exact against the CPU
+ *                          restatement FOR THE KERNEL USED: a caller who needs
+ *                          bit parity with a numpy / astropy pipeline passes
+ *                          that pipeline's array.
  *   out    [nf x ny x nx]
  * inf -> NaN, clip at vmax, astropy convolve() defaults (fill 0 boundary,
  * NaN-interpolating renormalised kernel), zeros -> np.nanmean, mask. */

@@ -33,24 +33,52 @@ int oi_launch_gather_rows(const double* xt, const double* yt, const double* tt, 
 
 namespace {
 
+// numpy's pairwise_sum of a[0 .. n): leaves of <= 128 elements with 8
+// accumulators, halves rounded down to multiples of 8.  n <= 8192 is one of
+// np.sum's iterator buffers, so this is arr.sum() for the ks*ks <= 4225 kernel
+// entries (oracle/day_oracle.py::numpy_pairwise_sum is the restatement).
+double np_pairwise_sum(const double* a, size_t n) {
+  if (n < 8) {
+    double res = 0.0;
+    for (size_t i = 0; i < n; ++i) res += a[i];
+    return res;
+  }
+  if (n <= 128) {
+    double r[8];
+    for (int k = 0; k < 8; ++k) r[k] = a[k];
+    size_t i = 8;
+    for (; i < n - (n % 8); i += 8)
+      for (int k = 0; k < 8; ++k) r[k] += a[i + k];
+    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; ++i) res += a[i];
+    return res;
+  }
+  size_t n2 = n / 2;
+  n2 -= n2 % 8;
+  return np_pairwise_sum(a, n2) + np_pairwise_sum(a + n2, n - n2);
+}
+
 // astropy Gaussian2DKernel(x_stddev=std): Gaussian2D(amplitude 1/(2 pi std^2),
-// theta 0) sampled at integer offsets, size 8*std rounded up to odd, / sum.
+// theta 0) sampled at integer offsets, size 8*std rounded up to odd, / sum, the
+// sum in numpy's order (arr.sum()).  What is left against numpy's array is
+// libm's exp against numpy's: entries within 4 ulp (tests/test_day_ref.py).
 std::vector<double> gaussian_kernel(double std_, int& ks) {
   int i = (int)std::ceil(8.0 * std_);
   ks = (i % 2 == 0) ? i + 1 : i;
   const int h = (ks - 1) / 2;
   const double a = 0.5 * (1.0 / (std_ * std_)), amp = 1.0 / (2 * M_PI * std_ * std_);
   std::vector<double> k((size_t)ks * ks);
-  double s = 0.0;
   for (int y = -h; y <= h; ++y)
-    for (int x = -h; x <= h; ++x) {
-      const double v = amp * std::exp(-((a * (double)(x * x)) + (a * (double)(y * y))));
-      k[(size_t)(y + h) * ks + (x + h)] = v;
-      s += v;
-    }
+    for (int x = -h; x <= h; ++x)
+      k[(size_t)(y + h) * ks + (x + h)] =
+          amp * std::exp(-((a * (double)(x * x)) + (a * (double)(y * y))));
+  const double s = np_pairwise_sum(k.data(), k.size());
   for (double& v : k) v /= s;
   return k;
 }
+
+// the std values oi_smooth_fields(kern = NULL) accepts (NaN refused)
+bool std_ok(double std_) { return std_ > 0.0 && std_ <= 8.0; }
 
 }  // namespace
 
@@ -67,7 +95,7 @@ int oi_smooth_fields(const double* fields, int32_t nf, int64_t ny, int64_t nx, c
     if (ks <= 0 || ks % 2 == 0 || ks > 65) return oi_set_last_error(OI_E_ARG, "kernel size must be odd, <= 65");
     kv.assign(kern, kern + (size_t)ks * ks);
   } else {
-    if (!(std_ > 0.0) || std_ > 8.0) return oi_set_last_error(OI_E_ARG, "std must be in (0, 8]");
+    if (!std_ok(std_)) return oi_set_last_error(OI_E_ARG, "std must be in (0, 8]");
     kv = gaussian_kernel(std_, ks);
   }
   const oi_options o = oi_resolve(opts);
@@ -172,6 +200,17 @@ int oi_gather_rows(const double* x_train, const double* y_train, const double* t
     HC(hipStreamSynchronize(st));
     return 0;
   });
+}
+
+// Test hook (not in oi.h): the kernel oi_smooth_fields(kern = NULL, std) builds.
+// Returns ks and writes the ks*ks entries when cap holds them; -1 for a std
+// that entry point refuses.  No GPU needed.
+int32_t oi_test_gaussian_kernel(double std_, double* out, int32_t cap) {
+  if (!std_ok(std_)) return -1;
+  int ks = 0;
+  const std::vector<double> k = gaussian_kernel(std_, ks);
+  if (out && (int64_t)cap >= (int64_t)k.size()) std::memcpy(out, k.data(), k.size() * 8);
+  return ks;
 }
 
 }  // extern "C"

@@ -20,7 +20,8 @@ from oracle import day_oracle as D
 from optimalinterpolation_amd import day, synthetic
 
 
-@pytest.mark.parametrize('n', [0, 1, 7, 8, 9, 127, 128, 129, 136, 1000, 8191, 8192, 8193, 20000, 102400])
+@pytest.mark.parametrize('n', [0, 1, 7, 8, 9, 127, 128, 129, 136, 1000, 8191, 8192, 8193, 20000, 102400,
+                               256 * 8192 + 8192 + 5])
 def test_numpy_summation_order(n):
     rng = np.random.default_rng(n)
     a = rng.normal(size=n) * rng.choice([1.0, 1e8, 1e-8], size=n)
