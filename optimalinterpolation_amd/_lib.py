@@ -106,6 +106,13 @@ SIGNATURES_LOO = {
                                   ctypes.POINTER(OiOptions)]),
 }
 
+# and for include/oi_lgo.h (tests/test_lgo_ref.py)
+SIGNATURES_LGO = {
+    'oi_gpr_lgo': (ctypes.c_int, [c_double_p, c_double_p, c_int64_p, ctypes.c_int64, c_int64_p, ctypes.c_double,
+                                  c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                  c_int32_p, ctypes.POINTER(OiOptions)]),
+}
+
 
 def load():
     """Load liboi.so (once).  Raises OiError when it has not been built."""
@@ -116,7 +123,8 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise OiError(f"{LIB_PATH} not built: run `make -C {_HERE}` (or __graft_entry__.build())")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in {**SIGNATURES, **SIGNATURES_NYSTROM_MULTI, **SIGNATURES_LOO}.items():
+        for name, (restype, argtypes) in {**SIGNATURES, **SIGNATURES_NYSTROM_MULTI, **SIGNATURES_LOO,
+                                          **SIGNATURES_LGO}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -330,6 +338,53 @@ def gpr_loo(xyt, z, offs, mean, hyp, lpl=True, device_inputs=False, **opt_kw):
 def gpr_loo_device(xyt_dev, z_dev, offs, mean, hyp, **kw):
     """gpr_loo(..., device_inputs=True)."""
     return gpr_loo(xyt_dev, z_dev, offs, mean, hyp, device_inputs=True, **kw)
+
+
+def gpr_lgo(xyt, z, offs, group, mean, hyp, lpd=True, d2=True, lpl=True, device_inputs=False, **opt_kw):
+    """oi_gpr_lgo: leave-group-out cross-validation of every cell at LINEAR
+    hypers ``hyp`` [ncell x 5], from one factorisation per cell.  ``group`` [N]
+    labels every observation (any int64; compared only inside a cell, only for
+    equality); every group is predicted jointly from the cell's observations
+    outside it.  Returns (mu [N], sd [N], lpd [N] | None, d2 [N] | None,
+    lpl [ncell] | None, status [ncell]): ``mu[i]`` / ``sd[i]`` are the predictive
+    mean and standard deviation of OBSERVATION i (noise included) given the
+    observations outside its group, in the observations' own order; ``lpd[i]``
+    and ``d2[i]`` are the joint log predictive density and the squared
+    Mahalanobis distance of i's group, repeated for every member; ``lpl`` sums
+    ``lpd`` over a cell's groups.  Status 1: the cell's factorisation failed
+    (all NaN); 2: some group's block failed to factor (those groups' rows and
+    ``lpl`` NaN).  With device_inputs=True ``xyt`` / ``z`` are fp64 contiguous
+    torch tensors on cuda:``device`` and the call runs on torch's current
+    stream; labels, offsets and hypers stay on the host."""
+    offs = _i64(offs)
+    ncell = len(offs) - 1
+    hyp = _f64(hyp).reshape(-1, 5)
+    if hyp.shape[0] != ncell:
+        raise ValueError("hyp must be [ncell x 5]")
+    dev = int(opt_kw.get('device', 0))
+    px, pz, _keep = _obs(xyt, z, offs, device_inputs, dev, what='z')
+    if device_inputs:
+        opt_kw.setdefault('stream', _caller_stream(dev))
+    N = int(offs[-1])
+    group = _i64(group)
+    if len(group) != N:
+        raise ValueError("group must label every observation")
+    mu = np.empty(N)
+    sd = np.empty(N)
+    lpda = np.empty(N) if lpd else None
+    d2a = np.empty(N) if d2 else None
+    lpla = np.empty(ncell) if lpl else None
+    status = np.zeros(ncell, dtype=np.int32)
+    o = options(device_inputs=device_inputs, **opt_kw)
+    _check(load().oi_gpr_lgo(px, pz, _ptr(offs, ctypes.c_int64), ncell, _ptr(group, ctypes.c_int64), float(mean),
+                             _ptr(hyp), _ptr(mu), _ptr(sd), _ptr(lpda), _ptr(d2a), _ptr(lpla),
+                             _ptr(status, ctypes.c_int32), ctypes.byref(o)))
+    return mu, sd, lpda, d2a, lpla, status
+
+
+def gpr_lgo_device(xyt_dev, z_dev, offs, group, mean, hyp, **kw):
+    """gpr_lgo(..., device_inputs=True)."""
+    return gpr_lgo(xyt_dev, z_dev, offs, group, mean, hyp, device_inputs=True, **kw)
 
 
 def split_cov(cov, toffs):

@@ -170,3 +170,42 @@ def loo_cells(cells, opt=True, x0=None, hyp=None, **kw):
     h = out8[:, 3:8] if opt else np.asarray(hyp, dtype=np.float64).reshape(-1, 5)
     mu, sd, lpl, st = _lib.gpr_loo(cells.xyt, cells.z, cells.offs, cells.mean, h, **o)
     return mu, sd, lpl, out8, np.maximum(status, st)
+
+
+def lgo_cells(cells, group, opt=True, x0=None, hyp=None, **kw):
+    """Leave-group-out cross-validation of every cell of a RaggedCells object
+    (``oi_gpr_lgo``: one factorisation per cell, not one per group).
+
+    ``group`` [N] labels every observation (any int64, compared inside a cell
+    only): a site (``site_groups``), a pass, a day, a satellite.  The fit is
+    exactly ``loo_cells``': ``opt=True`` fits the hypers as ``gpr_cells(opt=True)``
+    does and cross-validates at the fitted hypers; ``opt=False`` does so at
+    ``hyp`` [ncell x 5].  Returns ``(mu [N], sd [N], lpd [N], d2 [N], lpl [ncell],
+    out8, status)``: ``mu[i]`` / ``sd[i]`` predict observation i (noise included)
+    from the observations outside its group; ``lpd[i]`` / ``d2[i]`` are the joint
+    log density and the squared Mahalanobis distance (chi^2 with g degrees under
+    the model) of i's group, repeated for every member; ``lpl`` sums ``lpd`` over
+    a cell's groups; ``status[c]`` is the maximum of the fit's and the
+    cross-validation's."""
+    o = dict(options)
+    o.update(kw)
+    out8, status, _ = gpr_cells(cells, opt=opt, x0=x0, hyp=hyp, **kw)
+    h = out8[:, 3:8] if opt else np.asarray(hyp, dtype=np.float64).reshape(-1, 5)
+    mu, sd, lpd, d2, lpl, st = _lib.gpr_lgo(cells.xyt, cells.z, cells.offs, group, cells.mean, h, **o)
+    return mu, sd, lpd, d2, lpl, out8, np.maximum(status, st)
+
+
+def site_groups(xyt, offs):
+    """Labels [N] that join the bitwise-equal (x, y, t) rows of a cell -- the
+    observations of several satellites binned to one site -- for
+    leave-one-site-out through ``lgo_cells``.  A label is the batch row of the
+    site's first observation, so it is unique across cells too."""
+    xyt = np.ascontiguousarray(xyt, dtype=np.float64).reshape(-1, 3)
+    offs = np.asarray(offs, dtype=np.int64).reshape(-1)
+    bits = xyt.view(np.int64)    # equal bits, not equal values: -0.0 and 0.0 are two sites, a NaN equals itself
+    out = np.empty(len(xyt), dtype=np.int64)
+    for a, e in zip(offs[:-1], offs[1:]):
+        first = {}
+        for i in range(int(a), int(e)):
+            out[i] = first.setdefault(bits[i].tobytes(), i)
+    return out

@@ -20,6 +20,9 @@ cell 5) fits and predicts with:
 * ``GPR_loo(x, y, ell, sf2, sn2, mean)`` -- not in NB1: leave-one-out
   cross-validation of the full GP at the hypers NB1's GPR takes (mu, sd, log
   pseudo-likelihood; ``oi_gpr_loo``, one factorisation).
+* ``GPR_lgo(x, y, group, ell, sf2, sn2, mean)`` -- not in NB1: leave-group-out
+  cross-validation (every group of outputs predicted jointly from the rest;
+  ``oi_gpr_lgo``, one factorisation).
 * ``fit(x, y, M, x0=None)`` / ``fit_batch`` -- ``scipy.optimize.minimize(SMLII, x0,
   args=(x, y, True, M), method='CG', jac=True)`` (NB1 code cell 5) on the
   restated scipy CG of liboi.
@@ -177,6 +180,23 @@ def GPR_loo(x, y, ell, sf2, sn2, mean):
     if status[0] != 0:
         raise np.linalg.LinAlgError("Cholesky factorisation failed")
     return mean + mu, sd, lpl[0]
+
+
+def GPR_lgo(x, y, group, ell, sf2, sn2, mean):
+    """Leave-group-out cross-validation of one cell of the full GP in
+    ``GPR_loo``'s style: (mu [n], sd [n], lpd [n], d2 [n], lpl).  ``group`` [n]
+    labels the outputs; ``mu[i]`` / ``sd[i]`` predict output i (noise included)
+    from the outputs outside its group, ``lpd[i]`` / ``d2[i]`` are the joint log
+    density and squared Mahalanobis distance of i's group, and ``lpl`` the sum
+    of ``lpd`` over the groups.  LinAlgError where the cell's or a group's
+    Cholesky factorisation fails (``oi_gpr_lgo``)."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1, 3)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    hyp = np.array([[ell[0], ell[1], ell[2], sf2, sn2]], dtype=np.float64)
+    mu, sd, lpd, d2, lpl, status = _lib.gpr_lgo(x, y, [0, len(y)], group, 0.0, hyp, **options)
+    if status[0] != 0:
+        raise np.linalg.LinAlgError("Cholesky factorisation failed")
+    return mean + mu, sd, lpd, d2, lpl[0]
 
 
 def default_x0(grid_res=25):
