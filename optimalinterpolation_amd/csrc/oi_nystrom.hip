@@ -477,6 +477,13 @@ int check_batch(Batch& b) {
   return 0;
 }
 
+// the LINEAR hypers of ncell cells (5 each)
+int check_hypers(const double* hyp, int64_t ncell) {
+  for (int64_t q = 0; q < ncell * 5; ++q)
+    if (!(hyp[q] > 0.0)) return oi_set_last_error(OI_E_ARG, "hypers must be > 0");
+  return 0;
+}
+
 // One cell's inputs on the device: the row of the cell table a Runner reads.
 struct CellSrc {
   const double* x;     // n x 3
@@ -570,12 +577,97 @@ struct MultiDev {
   }
 };
 
-// objective pass: fused MFMA kernel (default) or, with OI_NYS_FUSED=0, the
-// n x n product forming Ki (oila::gemm) followed by k_nys_grad
-inline bool fused_objective() {
-  const char* e = getenv("OI_NYS_FUSED");
-  return !(e && atoi(e) == 0);
-}
+// The path's environment knobs, read once: by each Runner when it is built, by
+// the one-shot fit per call and by a session when it is created.
+struct Knobs {
+  // objective pass: fused MFMA kernel (default) or, with OI_NYS_FUSED=0, the
+  // n x n product forming Ki (oila::gemm) followed by k_nys_grad
+  bool fused = true;
+  // padding quantum (OI_NYS_PAD, default 32; 0 = no padding): K_mm and B of a
+  // cell are factored as diag(A, d I) of size Mp = M rounded up (the slot
+  // strides of the chunk arrays; results equal the unpadded path to rounding)
+  int padq = 32;
+  // the fit's groups of cells (OI_NYS_GROUPS), each with a stream and Runner of its own
+  int groups = 2;
+  // resident fitting cells per group of a session (OI_NYS_CAP): the batched
+  // eigensolver's per-column launches cost the same for 32 or 64 matrices, so a
+  // bigger chunk amortises them -- 5.46 / 6.69 / 6.63 cells/s at 32 / 64 / 128
+  // (--workload nystrom, one box, profiles/r05/nystrom_cap/)
+  int64_t cap = 64;
+  Knobs() {
+    if (const char* e = getenv("OI_NYS_FUSED")) fused = atoi(e) != 0;
+    if (const char* e = getenv("OI_NYS_PAD")) padq = std::max(0, atoi(e));
+    if (const char* e = getenv("OI_NYS_GROUPS")) groups = std::max(1, atoi(e));
+    if (const char* e = getenv("OI_NYS_CAP")) cap = std::max(1, atoi(e));
+  }
+};
+inline int64_t padded(int64_t M, int padq) { return padq > 0 ? up(M, padq) : M; }
+
+// A Runner's device memory is two workspaces, each described once by a layout
+// function (on a counting Carver: its size).
+//
+// Fixed: what one Runner owns for its lifetime -- the results and infos of an
+// evaluation's cells (at most cap) and phase 5's per-cell scratch, reused from
+// cell to cell in stream order.
+struct Fixed {
+  double* res;           // [cap x NRES]
+  int32_t* info;         // [cap x NINFO]
+  double *Av, *tv;       // A (n), W r (M)
+  double *Wp, *Ki;       // objective: W' packed (fused) or Ki (n x n), the other null
+  double* part;          // objective: the tiles' partial sums
+  double *ks, *kv, *xsc; // predict: k*, W k*, the scaled target
+  void layout(Carver& cv, int64_t nmax, int64_t mmax, int64_t cap, bool obj, bool pred, bool fused) {
+    const int64_t nt = blocks(nmax, 64);
+    res = cv.take(cap * NRES);
+    info = reinterpret_cast<int32_t*>(cv.take((cap * NINFO + 1) / 2));
+    Av = cv.take(nmax);
+    tv = cv.take(mmax);
+    Wp = obj && fused ? cv.take(blocks(mmax, 64) * nt * 4096) : nullptr;
+    Ki = obj && !fused ? cv.take(nmax * nmax) : nullptr;
+    part = obj ? cv.take(5 * nt * nt) : nullptr;
+    ks = pred ? cv.take(nmax) : nullptr;
+    kv = pred ? cv.take(mmax) : nullptr;
+    xsc = pred ? cv.take(3) : nullptr;
+  }
+  static int64_t doubles(int64_t nmax, int64_t mmax, int64_t cap, bool obj, bool pred, bool fused) {
+    Carver cv;
+    Fixed().layout(cv, nmax, mmax, cap, obj, pred, fused);
+    return cv.off;
+  }
+};
+
+// Slots: the per-slot state of a chunk of ch cells (scaled inputs, K_mm -> u,
+// s, st, C -> W', B -> L, the eigensolver's workspace, the Cholesky's
+// diagonal-block inverses, K_nm, U1 -> ut), each array ch slots of one stride;
+// Mp is the padded mmax.
+struct Slots {
+  struct Arr {
+    double* p = nullptr;
+    int64_t stride = 0;
+    double* slot(int64_t q) const { return p + q * stride; }
+  };
+  Arr sc, sq, Kmm, eval, stl, C, B, EW, Dinv, Knm, U1;
+  void layout(Carver& cv, int64_t ch, int64_t nmax, int64_t Mp) {
+    auto arr = [&](int64_t stride) { return Arr{cv.take(ch * stride), stride}; };
+    sc = arr(3 * nmax);
+    sq = arr(3 * nmax);
+    Kmm = arr(Mp * Mp);
+    eval = arr(Mp);
+    stl = arr(Mp);
+    C = arr(nmax * Mp);
+    B = arr(Mp * Mp);
+    EW = arr((int64_t)oila::eigh_workspace_doubles((int)Mp));
+    Dinv = arr((Mp + 63) / 64 * 4096);
+    Knm = arr(nmax * Mp);
+    U1 = arr(nmax * Mp);
+  }
+  // quantum 1 with ch = 1: one slot's share, what sizes a chunk
+  static int64_t doubles(int64_t ch, int64_t nmax, int64_t Mp, int64_t quantum = 32) {
+    Carver cv{nullptr, 0, quantum};
+    Slots().layout(cv, ch, nmax, Mp);
+    return cv.off;
+  }
+};
 
 // Evaluates any subset of a validated batch's cells at given LINEAR hypers.
 //
@@ -597,14 +689,12 @@ class Runner {
   // overlap); otherwise on the caller's opts.stream
   Runner(const std::vector<CellSrc>* tab, int64_t nmax, int64_t mmax, int64_t cap, const oi_options& o,
          bool want_obj, bool want_pred, bool own_stream = false)
-      : tab_(tab), nmax_(nmax), cap_(cap), st_((hipStream_t)o.stream), alloc_obj_(want_obj),
+      : tab_(tab), cap_(cap), st_((hipStream_t)o.stream), alloc_obj_(want_obj),
         alloc_pred_(want_pred) {
     if (own_stream) {
       own_.create();
       st_ = own_.s;
     }
-    res_.alloc(cap * NRES * 8);
-    info_.alloc(cap * NINFO * sizeof(int32_t));
     hres_.reserve(cap * NRES * 8);
     hinfo_.reserve(cap * NINFO * sizeof(int32_t));
     hr_ = hres_.as<double>();
@@ -612,52 +702,23 @@ class Runner {
     la_.bind(st_);
     sg_.on = o.profile != 0;
     sg_.st = st_;
-    // phase 5's per-cell scratch
-    const int64_t nt = blocks(nmax, 64);
-    Av_.alloc(nmax * 8);
-    tv_.alloc(mmax * 8);
-    if (want_obj) {
-      if (fused_objective()) {
-        Wp_.alloc((size_t)blocks(mmax, 64) * nt * 4096 * 8);
-      } else {
-        Ki_.alloc(nmax * nmax * 8);
-      }
-      part_.alloc(nt * nt * 5 * 8);
-    }
-    if (want_pred) {
-      ks_.alloc(nmax * 8);
-      kv_.alloc(mmax * 8);
-      xsc_.alloc(3 * 8);
-    }
-    // padding quantum (OI_NYS_PAD, default 32; 0 = no padding): K_mm and B of a
-    // cell are factored as diag(A, d I) of size Mp = M rounded up (the slot
-    // strides of the chunk arrays; results equal the unpadded path to rounding)
-    if (const char* e = getenv("OI_NYS_PAD")) padq_ = std::max(0, atoi(e));
-    mpmax_ = Mp(mmax);
-    // slot arrays: sc, sq (n x 3), Kmm (Mp^2), s, st (Mp), C, Knm, U1 (n x M), B (Mp^2),
-    // the eigensolver's workspace, the Cholesky's diagonal-block inverses;
-    // chunk <= 64 cells and <= 1/4 of the free HBM
-    const int64_t mmaxp = mpmax_;
-    ewd_ = oila::eigh_workspace_doubles((int)mmaxp);
-    nd64_ = (mmaxp + 63) / 64;
-    const size_t per = (size_t)(6 * nmax + 2 * mmaxp * mmaxp + 2 * mmaxp + 3 * nmax * mmaxp) * 8 +
-                       (ewd_ + (size_t)nd64_ * 4096) * 8;
+    const int64_t fd = Fixed::doubles(nmax, mmax, cap, want_obj, want_pred, kn_.fused);
+    fixed_.alloc((size_t)fd * 8);
+    Carver cf{fixed_.as<double>()};
+    fx_.layout(cf, nmax, mmax, cap, want_obj, want_pred, kn_.fused);
+    if (cf.off > fd) throw HipErr{"Runner: fixed workspace layout exceeds its estimate"};
+    // the slot arrays: chunk <= 64 cells and <= 1/4 of the HBM that is free now
+    // that the fixed part exists
+    const int64_t Mpmax = Mp(mmax);
+    const size_t per = (size_t)Slots::doubles(1, nmax, Mpmax, 1) * 8;
     size_t fr = 0, tot = 0;
     HC(hipMemGetInfo(&fr, &tot));
-    int64_t ch = std::min<int64_t>(64, cap);
-    ch = std::min<int64_t>(ch, std::max<int64_t>(1, (int64_t)(fr / 4 / per)));
-    chunk_ = ch;
-    sc_.alloc(ch * nmax * 3 * 8);
-    sq_.alloc(ch * nmax * 3 * 8);
-    Kmm_.alloc(ch * mmaxp * mmaxp * 8);
-    eval_.alloc(ch * mmaxp * 8);
-    stl_.alloc(ch * mmaxp * 8);
-    C_.alloc(ch * nmax * mmaxp * 8);
-    Knm_.alloc(ch * nmax * mmaxp * 8);
-    U1_.alloc(ch * nmax * mmaxp * 8);
-    B_.alloc(ch * mmaxp * mmaxp * 8);
-    EW_.alloc(ch * ewd_ * 8);
-    Dinv_.alloc(ch * nd64_ * 4096 * 8);
+    chunk_ = std::min<int64_t>(std::min<int64_t>(64, cap), std::max<int64_t>(1, (int64_t)(fr / 4 / per)));
+    const int64_t sd = Slots::doubles(chunk_, nmax, Mpmax);
+    slots_.alloc((size_t)sd * 8);
+    Carver cs{slots_.as<double>()};
+    sl_.layout(cs, chunk_, nmax, Mpmax);
+    if (cs.off > sd) throw HipErr{"Runner: slot workspace layout exceeds its estimate"};
   }
   ~Runner() {  // the members (buffers first, the stream last) go after the stream's work
     if (own_.s) (void)hipStreamSynchronize(own_.s);
@@ -672,6 +733,12 @@ class Runner {
            bool want_obj, bool want_pred) {
     enqueue(cells, hyp, mean, want_obj, want_pred);
     collect(out);
+  }
+  // the table's cells 0 .. ncell - 1
+  void run_all(int64_t ncell, const double* hyp, double mean, CellOut* out, bool want_obj, bool want_pred) {
+    std::vector<int64_t> cells(ncell);
+    for (int64_t c = 0; c < ncell; ++c) cells[c] = c;
+    run(cells, hyp, mean, out, want_obj, want_pred);
   }
 
   // queue one evaluation of cells[k] at hyp[k*5 ..] (copied) without waiting
@@ -696,8 +763,8 @@ class Runner {
     std::stable_sort(order_.begin(), order_.end(), [&](int64_t a, int64_t c) {
       return Mof(cells[a]) < Mof(cells[c]);
     });
-    HC(hipMemsetAsync(res_.p, 0, nc * NRES * 8, st_));
-    HC(hipMemsetAsync(info_.p, 0, nc * NINFO * sizeof(int32_t), st_));
+    HC(hipMemsetAsync(fx_.res, 0, nc * NRES * 8, st_));
+    HC(hipMemsetAsync(fx_.info, 0, nc * NINFO * sizeof(int32_t), st_));
     for (int64_t p0 = 0; p0 < nc; p0 += chunk_) {
       const int64_t p1 = std::min(nc, p0 + chunk_);
       for (int64_t p = p0; p < p1; ++p) phase1(p, p - p0);
@@ -706,8 +773,8 @@ class Runner {
       batched(p0, p1, 1);
       for (int64_t p = p0; p < p1; ++p) phase5(p, p - p0);
     }
-    HC(hipMemcpyAsync(hr_, res_.p, nc * NRES * 8, hipMemcpyDeviceToHost, st_));
-    HC(hipMemcpyAsync(hi_, info_.p, nc * NINFO * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+    HC(hipMemcpyAsync(hr_, fx_.res, nc * NRES * 8, hipMemcpyDeviceToHost, st_));
+    HC(hipMemcpyAsync(hi_, fx_.info, nc * NINFO * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
   }
 
   // wait for the queued evaluation; out[k] for the enqueued cells[k]
@@ -756,14 +823,13 @@ class Runner {
 
  private:
   int64_t Mof(int64_t c) const { return (*tab_)[c].M; }
-  int64_t Mp(int64_t M) const { return padq_ > 0 ? (M + padq_ - 1) / padq_ * padq_ : M; }
+  int64_t Mp(int64_t M) const { return padded(M, kn_.padq); }
 
   // which = 0: s, u = eigh(Kmm) (oila::eigh; u overwrites Kmm); 1: L = chol(B)
   // (oila::cholesky, in place, with the diagonal-block inverses kept for the
   // triangular solve) -- one batched call per run of slots with equal padded
   // size, on the main stream
   void batched(int64_t p0, int64_t p1, int which) {
-    const int64_t mm = mpmax_ * mpmax_;
     for (int64_t g0 = p0; g0 < p1;) {
       const int64_t M = Mp(Mof((*cells_)[order_[g0]]));  // padded size of the group
       int64_t g1 = g0 + 1;
@@ -774,9 +840,8 @@ class Runner {
       if (which == 0) {
         std::vector<oila::Eigh> es;
         for (int q = 0; q < cnt; ++q)
-          es.push_back(oila::Eigh{Kmm_.as<double>() + (s0 + q) * mm, eval_.as<double>() + (s0 + q) * mpmax_,
-                                  EW_.as<double>() + (s0 + q) * ewd_, iM, iM,
-                                  info_.as<int32_t>() + (g0 + q) * NINFO + 0});
+          es.push_back(oila::Eigh{sl_.Kmm.slot(s0 + q), sl_.eval.slot(s0 + q), sl_.EW.slot(s0 + q), iM, iM,
+                                  fx_.info + (g0 + q) * NINFO + 0});
         // algorithmic flops per phase: tridiagonalisation 4/3 M^3, tridiagonal
         // eigenpairs O(M^2), BCGS2 2 M^3, back-transform 2 M^3
         const double m3 = dM * dM * dM * cnt;
@@ -790,16 +855,13 @@ class Runner {
         // L = chol(B); half log-determinants; then W' = C L^-T by a block
         // triangular solve with the kept diagonal-block inverses
         sg_.begin(S_PANEL, dM * dM * dM / 3 * cnt, 0.0);
-        double* B0 = B_.as<double>() + s0 * mm;
         std::vector<oila::Chol> cs;
         for (int q = 0; q < cnt; ++q)
-          cs.push_back(oila::Chol{B0 + q * mm, Dinv_.as<double>() + (s0 + q) * nd64_ * 4096,
-                                  info_.as<int32_t>() + (g0 + q) * NINFO + 1, iM, iM});
+          cs.push_back(oila::Chol{sl_.B.slot(s0 + q), sl_.Dinv.slot(s0 + q), fx_.info + (g0 + q) * NINFO + 1, iM, iM});
         oila::cholesky(la_, st_, cs);
         // the pad block is the identity: log 1 = 0 and st is 1 there (see batched3)
-        hipLaunchKernelGGL(k_nys_logdet, dim3(cnt), dim3(256), 0, st_, B0, M, M, mm,
-                           stl_.as<double>() + s0 * mpmax_, mpmax_,
-                           res_.as<double>() + g0 * NRES, (int64_t)NRES);
+        hipLaunchKernelGGL(k_nys_logdet, dim3(cnt), dim3(256), 0, st_, sl_.B.slot(s0), M, M, sl_.B.stride,
+                           sl_.stl.slot(s0), sl_.stl.stride, fx_.res + g0 * NRES, (int64_t)NRES);
         KCHK();
         // W' = C L^-T in place on each slot's C (n x M, leading dimension n): one
         // batched right-looking block solve for the whole group
@@ -841,16 +903,15 @@ class Runner {
     R.r = (*tab_)[R.c].y;
     R.sl = (*tab_)[R.c].sel;
     R.hp = hyp_ + R.k * 5;
-    const int64_t nmax = nmax_, mmax = mpmax_;
-    R.sc = sc_.as<double>() + slot * nmax * 3;
-    R.sq = sq_.as<double>() + slot * nmax * 3;
-    R.Kmm = Kmm_.as<double>() + slot * mmax * mmax;
-    R.s = eval_.as<double>() + slot * mmax;
-    R.stl = stl_.as<double>() + slot * mmax;
-    R.C = C_.as<double>() + slot * nmax * mmax;
-    R.B = B_.as<double>() + slot * mmax * mmax;
-    R.rs = res_.as<double>() + p * NRES;
-    R.dinv = Dinv_.as<double>() + slot * nd64_ * 4096;
+    R.sc = sl_.sc.slot(slot);
+    R.sq = sl_.sq.slot(slot);
+    R.Kmm = sl_.Kmm.slot(slot);
+    R.s = sl_.eval.slot(slot);
+    R.stl = sl_.stl.slot(slot);
+    R.C = sl_.C.slot(slot);
+    R.B = sl_.B.slot(slot);
+    R.rs = fx_.res + p * NRES;
+    R.dinv = sl_.Dinv.slot(slot);
     return R;
   }
 
@@ -861,7 +922,6 @@ class Runner {
   // chip under-filled in the last wave of tiles)
   void batched3(int64_t p0, int64_t p1) {
     hipStream_t st = st_;
-    const int64_t nM = nmax_ * mpmax_;
     double fl = 0.0, by = 0.0;
     for (int64_t p = p0; p < p1; ++p) {
       const CellRefs R = refs(p, p - p0);
@@ -872,8 +932,8 @@ class Runner {
     std::vector<oila::Gemm> g1, g2;
     for (int64_t p = p0; p < p1; ++p) {
       const CellRefs R = refs(p, p - p0);
-      double* Knm = Knm_.as<double>() + (p - p0) * nM;
-      double* U1 = U1_.as<double>() + (p - p0) * nM;
+      double* Knm = sl_.Knm.slot(p - p0);
+      double* U1 = sl_.U1.slot(p - p0);
       hipLaunchKernelGGL(k_nys_eigpost, dim3(blocks(R.Mp, 256)), dim3(256), 0, st, R.s, R.M, R.Mp,
                          R.n, R.stl);
       KCHK();
@@ -886,7 +946,7 @@ class Runner {
     oila::gemm(la_, st, false, false, g1);
     for (int64_t p = p0; p < p1; ++p) {  // ut (in place of U1) and C
       const CellRefs R = refs(p, p - p0);
-      double* U1 = U1_.as<double>() + (p - p0) * nM;
+      double* U1 = sl_.U1.slot(p - p0);
       hipLaunchKernelGGL(k_nys_ut, dim3(blocks(R.n * R.M, 256)), dim3(256), 0, st, U1, R.n, R.M, R.s,
                          std::sqrt(R.dM / R.dn), 1.0 / R.hp[4], U1, R.C);
       KCHK();
@@ -934,8 +994,8 @@ class Runner {
     const double sf2 = R.hp[3], isn2 = 1.0 / R.hp[4];
     const double dn = R.dn, dM = R.dM;
     double* Wt = R.C;  // n x M: W' = C L^-T, formed in place by batched()
-    double* Av = Av_.as<double>();
-    double* tv = tv_.as<double>();
+    double* Av = fx_.Av;
+    double* tv = fx_.tv;
     StageTimer& sg = sg_;
     sg.begin(S_APPLY, 2.0 * dM * dM * dn + 4.0 * dn * dM, 16.0 * dn * dM);
     hipLaunchKernelGGL(k_nys_vi, dim3(blocks(R.n, 256)), dim3(256), 0, st, R.r, R.n, isn2, Av);
@@ -944,27 +1004,25 @@ class Runner {
     oila::gemv(la_, st, false, {oila::Gemv{Wt, tv, Av, R.in, R.iM, R.in, -1.0, 1.0}});   // A -= W' tv
     sg.end();
     if (obj_) {
-      double* Ki = Ki_.as<double>();
+      double* Ki = fx_.Ki;
       sg.begin(S_LOGDET, 2.0 * dn, 16.0 * dn);
       hipLaunchKernelGGL(k_nys_dot, dim3(1), dim3(256), 0, st, R.r, Av, R.n, R.rs + 0);
       KCHK();
       sg.end();
-      if (fused_objective()) {
+      if (kn_.fused) {
         // (W'W) tiles on the MFMA core, reduced against K, dK in the same kernel
         const int Tn = (int)blocks(R.n, 64), Tk = (int)blocks(R.M, 64);
         const int ntri = Tn * (Tn + 1) / 2;
         sg.begin(S_KI, dn * dn * dM, 8.0 * dn * dM);
         hipLaunchKernelGGL(k_nys_pack, dim3((unsigned)(Tn * Tk)), dim3(256), 0, st, Wt, R.n, R.M,
-                           Tn, Wp_.as<double>());
+                           Tn, fx_.Wp);
         KCHK();
         sg.end();
         sg.begin(S_GRAD, dn * dn * dM, 0.0);
-        hipLaunchKernelGGL(k_nys_grad_mfma, dim3((unsigned)ntri), dim3(256), 0, st,
-                           Wp_.as<double>(), Tn, Tk, Av, R.sc, R.sq, R.n, sf2, isn2,
-                           part_.as<double>());
+        hipLaunchKernelGGL(k_nys_grad_mfma, dim3((unsigned)ntri), dim3(256), 0, st, fx_.Wp, Tn, Tk, Av, R.sc,
+                           R.sq, R.n, sf2, isn2, fx_.part);
         KCHK();
-        hipLaunchKernelGGL(k_nys_partsum, dim3(1), dim3(256), 0, st, part_.as<double>(),
-                           (int64_t)ntri, R.rs + 2);
+        hipLaunchKernelGGL(k_nys_partsum, dim3(1), dim3(256), 0, st, fx_.part, (int64_t)ntri, R.rs + 2);
         KCHK();
         sg.end();
       } else {
@@ -979,11 +1037,9 @@ class Runner {
         // the lower triangle of Ki read once (~4 n^2 bytes); inputs and A cache-resident
         sg.begin(S_GRAD, 0.0, 4.0 * dn * dn);
         const unsigned nt = blocks(R.n, 64);
-        hipLaunchKernelGGL(k_nys_grad, dim3(nt, nt), dim3(256), 0, st, Ki, Av, R.sc, R.sq, R.n, sf2,
-                           part_.as<double>());
+        hipLaunchKernelGGL(k_nys_grad, dim3(nt, nt), dim3(256), 0, st, Ki, Av, R.sc, R.sq, R.n, sf2, fx_.part);
         KCHK();
-        hipLaunchKernelGGL(k_nys_partsum, dim3(1), dim3(256), 0, st, part_.as<double>(),
-                           (int64_t)nt * nt, R.rs + 2);
+        hipLaunchKernelGGL(k_nys_partsum, dim3(1), dim3(256), 0, st, fx_.part, (int64_t)nt * nt, R.rs + 2);
         KCHK();
         sg.end();
       }
@@ -991,13 +1047,13 @@ class Runner {
     if (pred_) {
       // k* = SGPkernel(x, xs=xs); fs = mean + k*.A; k*'Ki k* = |k*|^2/sn2 - |W k*|^2
       sg.begin(S_PRED, 2.0 * dn * dM, 8.0 * dn * dM);
-      double* ks = ks_.as<double>();
-      double* kv = kv_.as<double>();
+      double* ks = fx_.ks;
+      double* kv = fx_.kv;
       hipLaunchKernelGGL(k_nys_scale, dim3(1), dim3(64), 0, st, (*tab_)[R.c].xs,
-                         (int64_t)1, R.hp[0], R.hp[1], R.hp[2], xsc_.as<double>(), nullptr);
+                         (int64_t)1, R.hp[0], R.hp[1], R.hp[2], fx_.xsc, nullptr);
       KCHK();
       hipLaunchKernelGGL(k_nys_cross, dim3(blocks(R.n, 256), 1), dim3(256), 0, st, R.sc, nullptr,
-                         R.n, xsc_.as<double>(), nullptr, sf2, ks, R.n);
+                         R.n, fx_.xsc, nullptr, sf2, ks, R.n);
       KCHK();
       hipLaunchKernelGGL(k_nys_dot, dim3(1), dim3(256), 0, st, ks, Av, R.n, R.rs + 7);
       KCHK();
@@ -1046,18 +1102,15 @@ class Runner {
   }
 
   const std::vector<CellSrc>* tab_;
-  int64_t nmax_ = 0, cap_ = 0;
+  int64_t cap_ = 0;
+  const Knobs kn_;
   OwnStream own_;  // declared before every buffer: destroyed after them
   hipStream_t st_;
   bool obj_ = false, pred_ = false, alloc_obj_, alloc_pred_;
-  DevBuf res_, info_;
-  DevBuf sc_, sq_, Kmm_, eval_, stl_, C_, B_, EW_, Dinv_, Knm_, U1_;  // chunk-sized slot arrays
-  DevBuf Av_, tv_, Wp_, Ki_, part_, ks_, kv_, xsc_;                   // per-cell scratch
+  DevBuf fixed_, slots_;  // the two workspaces
+  Fixed fx_;              // ... and their arrays
+  Slots sl_;
   int64_t chunk_ = 1;
-  int padq_ = 32;
-  int64_t mpmax_ = 0;
-  size_t ewd_ = 0;
-  int64_t nd64_ = 0;
   oila::Stager la_;
   StageTimer sg_{kStage, S_COUNT};
   const std::vector<int64_t>* cells_ = nullptr;
@@ -1138,17 +1191,14 @@ extern "C" int oi_nystrom_batch(const double* xyt, const double* y, const int64_
     return oi_set_last_error(OI_E_ARG, "nlz and grad go together");
   const bool want_obj = nlz != nullptr, want_pred = pred != nullptr;
   if (want_pred && !xs) return oi_set_last_error(OI_E_ARG, "pred needs xs");
-  for (int64_t q = 0; q < ncell * 5; ++q)
-    if (!(hyp[q] > 0.0)) return oi_set_last_error(OI_E_ARG, "hypers must be > 0");
+  if (int rc = check_hypers(hyp, ncell)) return rc;
   const oi_options o = oi_resolve(opts);
   if (int rc = oi_select_device(o)) return rc;
   return oi_guarded([&] {
     BatchDev bd(b, want_pred ? xs : nullptr, o.device_inputs != 0, (hipStream_t)o.stream);
     Runner R(&bd.rows, b.nmax, b.mmax, ncell, o, want_obj, want_pred);
-    std::vector<int64_t> cells(ncell);
-    for (int64_t c = 0; c < ncell; ++c) cells[c] = c;
     std::vector<CellOut> out(ncell);
-    R.run(cells, hyp, mean, out.data(), want_obj, want_pred);
+    R.run_all(ncell, hyp, mean, out.data(), want_obj, want_pred);
     for (int64_t c = 0; c < ncell; ++c) {
       status[c] = out[c].status;
       if (want_obj) {
@@ -1172,6 +1222,21 @@ int64_t oi_nystrom_multi_cell_doubles(int64_t n, int64_t M, int64_t nt, bool cov
   return MultiDev::doubles(0, -1, s) + (cov ? nt * nt : 0);
 }
 
+// Test hook (declared in no header, touches no device): a Runner's workspaces
+// in doubles.  which 0: Fixed for cap cells (flags: 1 objective, 2 predict,
+// 4 fused); 1: Slots for ch slots as allocated; 2: one slot unrounded, what
+// sizes a chunk.  -1 for anything else.
+extern "C" int64_t oi_test_nystrom_runner_doubles(int32_t which, int64_t nmax, int64_t mmax, int64_t cap_or_ch,
+                                                  int32_t padq, int32_t flags) {
+  if (nmax < 0 || mmax < 0 || mmax > INT32_MAX / 2 || cap_or_ch < 0 || padq < 0) return -1;
+  switch (which) {
+    case 0: return Fixed::doubles(nmax, mmax, cap_or_ch, flags & 1, flags & 2, flags & 4);
+    case 1: return Slots::doubles(cap_or_ch, nmax, padded(mmax, padq));
+    case 2: return Slots::doubles(1, nmax, padded(mmax, padq), 1);
+  }
+  return -1;
+}
+
 extern "C" int oi_nystrom_predict_multi(const double* xyt, const double* y, const int64_t* offs,
                                         int64_t ncell, const int64_t* sel, const int64_t* soffs,
                                         const double* hyp, const double* xs, const int64_t* toffs,
@@ -1185,8 +1250,7 @@ extern "C" int oi_nystrom_predict_multi(const double* xyt, const double* y, cons
   if (!status) return oi_set_last_error(OI_E_ARG, "null status");
   const int64_t T = toffs[ncell];
   if (T > 0 && (!xs || !fs || !sd)) return oi_set_last_error(OI_E_ARG, "null xs / fs / sd");
-  for (int64_t q = 0; q < ncell * 5; ++q)
-    if (!(hyp[q] > 0.0)) return oi_set_last_error(OI_E_ARG, "hypers must be > 0");
+  if (int rc = check_hypers(hyp, ncell)) return rc;
   // oila's operands take 32-bit byte offsets: Kxsx and cov stay below 2 GiB each
   constexpr int64_t LIM = 0x7FFFFFF0 / 8;
   std::vector<int64_t> coffs(ncell + 1, 0);
@@ -1226,9 +1290,7 @@ extern "C" int oi_nystrom_predict_multi(const double* xyt, const double* y, cons
     {
       Runner R(&bd.rows, b.nmax, b.mmax, ncell, o, false, false);
       R.set_multi(&md);
-      std::vector<int64_t> cells(ncell);
-      for (int64_t c = 0; c < ncell; ++c) cells[c] = c;
-      R.run(cells, hyp, mean, out.data(), false, false);
+      R.run_all(ncell, hyp, mean, out.data(), false, false);
     }
     // nothing was written so far: every output in one go, once all cells are done
     if (T > 0) {
@@ -1281,9 +1343,7 @@ extern "C" int oi_nystrom_fit_batch(const double* xyt, const double* y, const in
     // each with its own stream, so one group's latency-bound batched
     // eigh overlaps the other's panels / objective pass; each group is
     // collected and re-queued as soon as its round is done
-    int G = 2;
-    if (const char* e = getenv("OI_NYS_GROUPS")) G = atoi(e);
-    G = std::max(1, std::min<int>(G, (int)ncell));
+    const int G = (int)std::min<int64_t>(Knobs().groups, ncell);
     std::vector<std::vector<int64_t>> gcells(G);
     for (int64_t c = 0; c < ncell; ++c) gcells[c % G].push_back(c);
     BatchDev bd(b, xs, o.device_inputs != 0, (hipStream_t)o.stream);
@@ -1319,13 +1379,9 @@ extern "C" int oi_nystrom_fit_batch(const double* xyt, const double* y, const in
     RG.clear();
     Runner R(&bd.rows, b.nmax, b.mmax, ncell, o, false, true);
     // NB1 code cell 5: GPR(approx=True) at the fitted hypers
-    std::vector<int64_t> cells(ncell);
     std::vector<double> hyp(ncell * 5);
-    for (int64_t c = 0; c < ncell; ++c) {
-      cells[c] = c;
-      cg_readout(cg[c], hyp.data() + c * 5, info ? info + c * 4 : nullptr);
-    }
-    R.run(cells, hyp.data(), mean, res.data(), false, true);
+    for (int64_t c = 0; c < ncell; ++c) cg_readout(cg[c], hyp.data() + c * 5, info ? info + c * 4 : nullptr);
+    R.run_all(ncell, hyp.data(), mean, res.data(), false, true);
     for (int64_t c = 0; c < ncell; ++c) write_fit(res[c], hyp.data() + c * 5, out + c * 8, status + c);
     return 0;
   });
@@ -1354,12 +1410,7 @@ struct NysTicket {
 
 struct oi_nystrom_session {
   oi_options o;
-  int G = 2;
-  // resident fitting cells per group (OI_NYS_CAP): the batched eigensolver's
-  // per-column launches cost the same for 32 or 64 matrices, so a bigger chunk
-  // amortises them -- 5.46 / 6.69 / 6.63 cells/s at 32 / 64 / 128
-  // (--workload nystrom, one box, profiles/r05/nystrom_cap/)
-  int64_t cap = 64;
+  const Knobs kn;  // as the environment was at create: kn.groups groups of up to kn.cap fitting cells
   int32_t maxiter = 1000;
   double gtol = 1e-5;
   std::vector<CellSrc> tab;          // every submitted cell, by global id
@@ -1393,9 +1444,9 @@ struct oi_nystrom_session {
   void build_runners(int64_t nm, int64_t mm) {
     nmax = std::max(nmax, nm);
     mmax = std::max(mmax, mm);
-    grp.resize(G);
-    for (auto& g : grp) g.R.reset(new Runner(&tab, nmax, mmax, cap, o, true, false, G > 1));
-    pred.reset(new Runner(&tab, nmax, mmax, cap, o, false, true, true));
+    grp.resize(kn.groups);
+    for (auto& g : grp) g.R.reset(new Runner(&tab, nmax, mmax, kn.cap, o, true, false, kn.groups > 1));
+    pred.reset(new Runner(&tab, nmax, mmax, kn.cap, o, false, true, true));
   }
 
   void feed(Grp& g) {  // collect a group's round, advance its cells' CG
@@ -1424,6 +1475,7 @@ struct oi_nystrom_session {
   void complete(NysTicket& t) {
     // GPR(approx=True) at the fitted hypers, in chunks of the Runner capacity
     Runner& R = *pred;
+    const int64_t cap = kn.cap;
     std::vector<CellOut> res(cap);
     for (int64_t a = 0; a < t.count; a += cap) {
       const int64_t b = std::min(t.count, a + cap);
@@ -1446,7 +1498,7 @@ struct oi_nystrom_session {
   }
 
   void admit(Grp& g) {
-    while ((int64_t)g.active.size() < cap && !queue.empty()) {
+    while ((int64_t)g.active.size() < kn.cap && !queue.empty()) {
       const int64_t c = queue.front();
       queue.pop_front();
       if (cg_start(cg[c], x0.data() + c * 5, gtol, maxiter, req.data() + c * 6))
@@ -1503,8 +1555,6 @@ extern "C" oi_nystrom_session* oi_nystrom_session_create(const oi_options* opts)
     return nullptr;
   s->maxiter = o.maxiter < 0 ? 1000 : o.maxiter;  // scipy: len(x0) * 200 for NB1's 5 hypers
   s->gtol = o.gtol;
-  if (const char* e = getenv("OI_NYS_GROUPS")) s->G = std::max(1, atoi(e));
-  if (const char* e = getenv("OI_NYS_CAP")) s->cap = std::max(1, atoi(e));
   return s.release();
 }
 
