@@ -113,6 +113,14 @@ SIGNATURES_LGO = {
                                   c_int32_p, ctypes.POINTER(OiOptions)]),
 }
 
+# and for include/oi_sample.h (tests/test_sample_abi.py)
+SIGNATURES_SAMPLE = {
+    'oi_gpr_sample': (ctypes.c_int, [c_double_p, c_double_p, c_int64_p, ctypes.c_int64, c_double_p, c_int64_p,
+                                     ctypes.c_double, c_double_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
+                                     ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), c_double_p, c_double_p,
+                                     c_double_p, c_double_p, c_int32_p, ctypes.POINTER(OiOptions)]),
+}
+
 
 def load():
     """Load liboi.so (once).  Raises OiError when it has not been built."""
@@ -124,7 +132,7 @@ def load():
             raise OiError(f"{LIB_PATH} not built: run `make -C {_HERE}` (or __graft_entry__.build())")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in {**SIGNATURES, **SIGNATURES_NYSTROM_MULTI, **SIGNATURES_LOO,
-                                          **SIGNATURES_LGO}.items():
+                                          **SIGNATURES_LGO, **SIGNATURES_SAMPLE}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -385,6 +393,66 @@ def gpr_lgo(xyt, z, offs, group, mean, hyp, lpd=True, d2=True, lpl=True, device_
 def gpr_lgo_device(xyt_dev, z_dev, offs, group, mean, hyp, **kw):
     """gpr_lgo(..., device_inputs=True)."""
     return gpr_lgo(xyt_dev, z_dev, offs, group, mean, hyp, device_inputs=True, **kw)
+
+
+def gpr_sample(xyt, z, offs, xs, toffs, mean, hyp, nsamp, noise=False, jitter=0.0, seed=0, streams=None, xi=None,
+               device_inputs=False, **opt_kw):
+    """oi_gpr_sample: ``nsamp`` joint draws from every cell's posterior at its
+    own targets (``xs`` [T x 3], cell c owning rows toffs[c]:toffs[c+1]) at
+    LINEAR hypers ``hyp`` [ncell x 5].  Returns (samples [T x nsamp], fs [T],
+    sd [T], status [ncell]): row ``toffs[c] + t`` of ``samples`` holds the draws
+    at target t of cell c, column s is draw s, and the columns of a cell are
+    jointly normal with mean ``fs`` and the posterior covariance of
+    ``gpr_predict_multi(cov=True)`` (plus sn2 on its diagonal with ``noise``:
+    draws of new observations; plus the absolute variance ``jitter``).  With
+    ``xi`` [T x nsamp] the standard normals are the caller's; otherwise they are
+    generated on the device from ``seed`` and the cells' 64-bit ``streams``
+    [ncell] (default: the cell's index in the call), so that a cell's draws
+    depend only on (seed, its stream, its number of targets, the columns asked
+    for).  Status 1: the cell's factorisation failed (all NaN); 2: the posterior
+    covariance did not factor (NaN samples, valid fs and sd; add ``jitter`` or
+    ``noise``).  With device_inputs=True ``xyt`` / ``z`` are fp64 contiguous
+    torch tensors on cuda:``device`` and the call runs on torch's current
+    stream; everything else stays on the host."""
+    offs, toffs = _i64(offs), _i64(toffs)
+    xs = _f64(xs).reshape(-1, 3)
+    ncell = len(offs) - 1
+    if len(toffs) != ncell + 1 or toffs[0] != 0 or toffs[-1] != xs.shape[0]:
+        raise ValueError("inconsistent ragged batch")
+    hyp = _f64(hyp).reshape(-1, 5)
+    if hyp.shape[0] != ncell:
+        raise ValueError("hyp must be [ncell x 5]")
+    nsamp = int(nsamp)
+    if nsamp < 0:
+        raise ValueError("nsamp must be >= 0")
+    T = int(toffs[-1])
+    if streams is not None:
+        streams = np.ascontiguousarray(streams, dtype=np.uint64).reshape(-1)
+        if len(streams) != ncell:
+            raise ValueError("streams must be [ncell]")
+    if xi is not None:
+        xi = _f64(xi)
+        if xi.size != T * nsamp:
+            raise ValueError("xi must be [T x nsamp]")
+    dev = int(opt_kw.get('device', 0))
+    px, pz, _keep = _obs(xyt, z, offs, device_inputs, dev, what='z')
+    if device_inputs:
+        opt_kw.setdefault('stream', _caller_stream(dev))
+    samples = np.empty((T, nsamp))
+    fs = np.empty(T)
+    sd = np.empty(T)
+    status = np.zeros(ncell, dtype=np.int32)
+    o = options(device_inputs=device_inputs, **opt_kw)
+    _check(load().oi_gpr_sample(px, pz, _ptr(offs, ctypes.c_int64), ncell, _ptr(xs), _ptr(toffs, ctypes.c_int64),
+                                float(mean), _ptr(hyp), nsamp, 1 if noise else 0, float(jitter),
+                                int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(streams, ctypes.c_uint64), _ptr(xi),
+                                _ptr(samples), _ptr(fs), _ptr(sd), _ptr(status, ctypes.c_int32), ctypes.byref(o)))
+    return samples, fs, sd, status
+
+
+def gpr_sample_device(xyt_dev, z_dev, offs, xs, toffs, mean, hyp, nsamp, **kw):
+    """gpr_sample(..., device_inputs=True)."""
+    return gpr_sample(xyt_dev, z_dev, offs, xs, toffs, mean, hyp, nsamp, device_inputs=True, **kw)
 
 
 def split_cov(cov, toffs):

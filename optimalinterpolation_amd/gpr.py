@@ -195,6 +195,31 @@ def lgo_cells(cells, group, opt=True, x0=None, hyp=None, **kw):
     return mu, sd, lpd, d2, lpl, out8, np.maximum(status, st)
 
 
+def sample_cells(cells, xs, toffs, nsamp, opt=True, x0=None, hyp=None, **kw):
+    """Joint posterior draws for every cell of a RaggedCells object at its own
+    list of targets (``oi_gpr_sample``; ``xs`` [T x 3], cell c owning rows
+    toffs[c]:toffs[c+1]).
+
+    The fit is exactly ``loo_cells``': ``opt=True`` fits the hypers as
+    ``gpr_cells(opt=True)`` does and draws at the fitted hypers; ``opt=False``
+    draws at ``hyp`` [ncell x 5].  ``noise``, ``jitter``, ``seed``, ``streams``
+    and ``xi`` go to ``_lib.gpr_sample`` (pass the grid-cell indices as
+    ``streams`` so that sharding the cells does not change a draw); the other
+    keywords are options.  Returns ``(samples [T x nsamp], fs [T], sd [T],
+    out8, status)``: column s of a cell's rows of ``samples`` is one joint
+    realisation of the field at the cell's targets, ``fs`` / ``sd`` are
+    ``gpr_predict_multi``'s, ``out8`` is what ``gpr_cells`` returns, and
+    ``status[c]`` the maximum of the fit's and the draw's."""
+    draw = {k: kw.pop(k) for k in ('noise', 'jitter', 'seed', 'streams', 'xi') if k in kw}
+    o = dict(options)
+    o.update(kw)
+    out8, status, _ = gpr_cells(cells, opt=opt, x0=x0, hyp=hyp, **kw)
+    h = out8[:, 3:8] if opt else np.asarray(hyp, dtype=np.float64).reshape(-1, 5)
+    samples, fs, sd, st = _lib.gpr_sample(cells.xyt, cells.z, cells.offs, xs, toffs, cells.mean, h, nsamp,
+                                          **draw, **o)
+    return samples, fs, sd, out8, np.maximum(status, st)
+
+
 def site_groups(xyt, offs):
     """Labels [N] that join the bitwise-equal (x, y, t) rows of a cell -- the
     observations of several satellites binned to one site -- for

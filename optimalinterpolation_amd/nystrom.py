@@ -182,6 +182,25 @@ def GPR_loo(x, y, ell, sf2, sn2, mean):
     return mean + mu, sd, lpl[0]
 
 
+def GPR_sample(x, y, xs, ell, sf2, sn2, mean, nsamp, seed=0, noise=False):
+    """``nsamp`` joint draws from one cell's full-GP posterior at the targets
+    ``xs`` [ns x 3] in NB1 GPR's argument style (``y`` the residual outputs,
+    ``mean`` added back): (samples [ns x nsamp], fs [ns], sd [ns]).  Column s of
+    ``samples`` is one realisation of the field (of new observations with
+    ``noise``) at all targets; ``fs`` / ``sd`` are ``GPR``'s.  LinAlgError where
+    the cell's Cholesky factorisation or the posterior covariance's fails
+    (``oi_gpr_sample``)."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1, 3)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    xs = np.asarray(xs, dtype=np.float64).reshape(-1, 3)
+    hyp = np.array([[ell[0], ell[1], ell[2], sf2, sn2]], dtype=np.float64)
+    samples, f0, sd, status = _lib.gpr_sample(x, y, [0, len(y)], xs, [0, len(xs)], 0.0, hyp, nsamp, noise=noise,
+                                              seed=seed, **options)
+    if status[0] != 0:
+        raise np.linalg.LinAlgError("Cholesky factorisation failed")
+    return mean + samples, mean + f0, sd
+
+
 def GPR_lgo(x, y, group, ell, sf2, sn2, mean):
     """Leave-group-out cross-validation of one cell of the full GP in
     ``GPR_loo``'s style: (mu [n], sd [n], lpd [n], d2 [n], lpl).  ``group`` [n]
