@@ -78,6 +78,15 @@ int oi_gpr_batch(const double* xyt, const double* z, const int64_t* offs, int64_
                  const double* hyp, double* out, int32_t* status, int32_t* info,
                  const oi_options* opts);
 
+/* Workspace of the engine entries (oi_gpr_batch, oi_nlml_grad_batch,
+ * oi_session_*): opts->pool_bytes is the device arena the resident cells'
+ * tiles are carved from and opts->max_pool the number of cells resident at
+ * once; a batch is refused at submission, before any launch, with OI_E_NOMEM
+ * ("a cell needs ...") when its largest cell alone exceeds the pool.  A batch
+ * that passes this check completes, in a pool of exactly that cell too: cells
+ * wait their turn for slots and memory, and the batch's staged inputs, which
+ * share the arena while it has room, may live outside the pool. */
+
 /* Stream ordering (opts->device_inputs = 1): device inputs are read on
  * opts->stream when it is set; with stream == NULL the library's own stream
  * first waits for the legacy NULL stream (PyTorch's default stream), so any

@@ -28,6 +28,7 @@
 
 #include "../../include/oi.h"
 #include "cg.hpp"
+#include "oi_arena.h"
 #include "oi_device.h"
 #include "oi_host.h"
 #include "oi_masks.h"
@@ -44,57 +45,26 @@ int fail(int code, const std::string& msg) {
 inline int tiles_of(int64_t n) { return (int)((n + OI_NB - 1) / OI_NB); }
 
 // ------------------------------------------------------------- arena
-// First-fit free list over one device allocation (256-byte granules).
+// One device allocation behind the first-fit free list of oi_arena.h (the
+// list's rules, zero-byte blocks among them, are stated and checked there).
 class Arena {
  public:
   void init(size_t bytes) {
     HC(hipMalloc(&base_, bytes));
-    size_ = bytes;
-    free_.clear();
-    free_[0] = bytes;
+    list_.reset(bytes);
   }
   ~Arena() {
     if (base_) (void)hipFree(base_);
   }
-  size_t size() const { return size_; }
-  // returns offset or SIZE_MAX
-  size_t alloc(size_t bytes) {
-    bytes = (bytes + 255) & ~size_t(255);
-    for (auto it = free_.begin(); it != free_.end(); ++it) {
-      if (it->second >= bytes) {
-        size_t off = it->first, len = it->second;
-        free_.erase(it);
-        if (len > bytes) free_[off + bytes] = len - bytes;
-        return off;
-      }
-    }
-    return SIZE_MAX;
-  }
-  void release(size_t off, size_t bytes) {
-    bytes = (bytes + 255) & ~size_t(255);
-    // a block the arena never handed out (SIZE_MAX = a failed alloc) must not
-    // enter the free list: it would alias live allocations after wrap-around
-    if (off >= size_ || bytes > size_ - off) return;
-    auto it = free_.emplace(off, bytes).first;
-    auto nx = std::next(it);
-    if (nx != free_.end() && it->first + it->second == nx->first) {
-      it->second += nx->second;
-      free_.erase(nx);
-    }
-    if (it != free_.begin()) {
-      auto pv = std::prev(it);
-      if (pv->first + pv->second == it->first) {
-        pv->second += it->second;
-        free_.erase(it);
-      }
-    }
-  }
+  size_t size() const { return list_.size(); }
+  size_t alloc(size_t bytes) { return list_.alloc(bytes); }  // offset or SIZE_MAX
+  void release(size_t off, size_t bytes) { list_.release(off, bytes); }
   char* ptr(size_t off) const { return static_cast<char*>(base_) + off; }
+  const OiFreeList& list() const { return list_; }
 
  private:
   void* base_ = nullptr;
-  size_t size_ = 0;
-  std::map<size_t, size_t> free_;
+  OiFreeList list_;
 };
 
 size_t cell_bytes(int64_t n, bool eval) {
@@ -107,6 +77,24 @@ size_t cell_bytes(int64_t n, bool eval) {
   add(4 * T * OI_NB * 8);                        // vec
   add((size_t)OI_PART_SIZE(nt, T) * 8);          // part
   return b;
+}
+
+// The device block of a submitted batch of N observations in nc cells, its
+// pieces rounded to 256 bytes: residuals | sites | v | d | offs | m | SSW, and
+// the rows' own copy when the inputs come from the host.
+struct InputSizes {
+  size_t sz[8];
+  size_t total() const {
+    size_t b = 0;
+    for (size_t x : sz) b += x;
+    return b;
+  }
+};
+InputSizes input_sizes(int64_t N, int64_t nc, bool host_inputs) {
+  auto rnd = [](size_t b) { return (b + 255) & ~size_t(255); };
+  const size_t N1 = (size_t)std::max<int64_t>(N, 1), C1 = (size_t)std::max<int64_t>(nc, 1);
+  return {{rnd(N1 * 8), rnd(N1 * 24), rnd(N1 * 8), rnd(N1 * 8), rnd((C1 + 1) * 8), rnd(C1 * 4), rnd(C1 * 8),
+           host_inputs ? rnd(N1 * 24) : 0}};
 }
 
 // ------------------------------------------------------------- profiling
@@ -562,12 +550,9 @@ class Engine {
     // drain the GPU once per batch).  Arena blocks are released only after the
     // rounds that used them completed, so the new block never overlaps them.
     // one block: residuals | sites | v | d | offs | m | SSW (| host inputs' copy)
-    auto rnd = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t N1 = (size_t)std::max<int64_t>(N, 1), C1 = (size_t)std::max<int64_t>(nc, 1);
-    const size_t sz[8] = {rnd(N1 * 8), rnd(N1 * 24), rnd(N1 * 8), rnd(N1 * 8), rnd((C1 + 1) * 8),
-                          rnd(C1 * 4), rnd(C1 * 8), o_.device_inputs ? 0 : rnd(N1 * 24)};
-    jb.in_bytes = 0;
-    for (size_t b : sz) jb.in_bytes += b;
+    const InputSizes in = input_sizes(N, nc, !o_.device_inputs);
+    const size_t* sz = in.sz;
+    jb.in_bytes = in.total();
     jb.in_off = ctx_.arena.alloc(jb.in_bytes);
     char* base;
     if (jb.in_off != SIZE_MAX) {
@@ -681,6 +666,8 @@ class Engine {
       }
       if (id >= 0 ? done(id) : (jobs_.empty() && !any)) break;
       if (!any) {
+        // (admit() moved the queued inputs out of the arena first: this is left
+        // for inputs whose own buffer could not be allocated)
         if (!queue_.empty()) throw NoMem{"workspace exhausted with no resident cell"};
         break;
       }
@@ -724,6 +711,50 @@ class Engine {
     if (it != jobs_.end()) jobs_.erase(it);  // frees the job (its own DevBuf, if any)
   }
 
+  bool nothing_resident() const {
+    for (const Group& gr : groups_)
+      if (!gr.active.empty()) return false;
+    return true;
+  }
+
+  // Moves the input block of every batch out of the arena into the batch's own
+  // buffer and returns whether the arena gained anything.  Only with nothing
+  // resident (so no round in flight reads the blocks): queued cells take their
+  // pointers from the job at admission.  A batch whose buffer cannot be
+  // allocated keeps its block.
+  bool evict_inputs() {
+    std::vector<Job*> moved;
+    for (auto& kv : jobs_) {
+      Job& jb = *kv.second;
+      if (jb.in_off == SIZE_MAX) continue;
+      try {
+        jb.own.reserve(jb.in_bytes);
+      } catch (const HipErr&) {
+        (void)hipGetLastError();
+        continue;
+      }
+      HC(hipMemcpyAsync(jb.own.p, ctx_.arena.ptr(jb.in_off), jb.in_bytes, hipMemcpyDeviceToDevice, ss_));
+      moved.push_back(&jb);
+    }
+    if (moved.empty()) return false;
+    HC(hipStreamSynchronize(ss_));
+    for (Job* jp : moved) {
+      const char* from = ctx_.arena.ptr(jp->in_off);
+      auto move = [&](const double*& p) {  // (xyt is the caller's with device inputs)
+        const char* q = (const char*)p;
+        if (q >= from && q < from + jp->in_bytes) p = (const double*)((const char*)jp->own.p + (q - from));
+      };
+      move(jp->xyt);
+      move(jp->r);
+      move(jp->sites);
+      move(jp->v);
+      move(jp->dw);
+      ctx_.arena.release(jp->in_off, jp->in_bytes);
+      jp->in_off = SIZE_MAX;
+    }
+    return true;
+  }
+
   void admit(Group& gr) {
     while (!queue_.empty() && !gr.free_slots.empty()) {
       Job* jp = queue_.front().first;
@@ -732,7 +763,12 @@ class Engine {
       const int64_t n = job.m[c];  // the cell's problem size: its distinct sites
       const bool eval_mem = job.kind != Job::PREDICT_ONLY;
       const size_t bytes = cell_bytes(n, eval_mem);
-      const size_t off = ctx_.arena.alloc(bytes);
+      size_t off = ctx_.arena.alloc(bytes);
+      // The head cell passed submit's check against the whole pool, yet with
+      // nothing resident no release will ever make room for it: what stands in
+      // its way are the queued batches' input blocks.  Move those out of the
+      // arena and try once more.
+      if (off == SIZE_MAX && nothing_resident() && evict_inputs()) off = ctx_.arena.alloc(bytes);
       if (off == SIZE_MAX) break;
       queue_.pop_front();
       const int s = gr.free_slots.back();
@@ -1337,6 +1373,31 @@ int64_t oi_profile_json(char* buf, int64_t len) {
     buf[len - 1] = 0;
   }
   return (int64_t)s.size() + 1;
+}
+
+// ---- test hooks (exported, not part of include/oi.h): the engine's sizes, from
+// the functions admit() and submit() size by, and the state of a device's arena
+int64_t oi_test_engine_cell_bytes(int64_t n, int32_t eval) { return (int64_t)cell_bytes(n, eval != 0); }
+
+int64_t oi_test_engine_input_bytes(int64_t N, int64_t ncell, int32_t host_inputs) {
+  return (int64_t)input_sizes(N, ncell, host_inputs != 0).total();
+}
+
+// out = {size, free bytes, largest free block} of the device's context; -1
+// (and out all -1) when no call has made one yet
+int32_t oi_test_engine_arena(int32_t device, int64_t* out) {
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
+  auto it = g_ctx.find(device);
+  if (it == g_ctx.end() || !it->second) {
+    out[0] = out[1] = out[2] = -1;
+    return -1;
+  }
+  std::lock_guard<std::mutex> cl(it->second->mu);
+  const OiFreeList& fl = it->second->arena.list();
+  out[0] = (int64_t)fl.size();
+  out[1] = (int64_t)fl.free_bytes();
+  out[2] = (int64_t)fl.largest_free();
+  return 0;
 }
 
 void oi_profile_reset(void) {
