@@ -120,6 +120,125 @@ int oi_gpr_predict_multi(const double* xyt, const double* z, const int64_t* offs
                          double* fs, double* sd, double* lz, double* cov,
                          int32_t* status, const oi_options* opts);
 
+/* Leave-one-out prediction of every observation of every cell from the cell's
+ * other observations, at given LINEAR hypers (Rasmussen & Williams, GPML
+ * 5.4.2), from one factorisation per cell:
+ *   r = z - mean, K~ = K + sn2 I = L L', alpha = K~^-1 r, q_i = [K~^-1]_ii
+ *   mu_i = z_i - alpha_i / q_i, sd_i = sqrt(1 / q_i)
+ *   lpl  = sum_i [ -log(2 pi)/2 - log sd_i - (z_i - mu_i)^2 / (2 sd_i^2) ]
+ * mu_i and sd_i are the predictive mean and standard deviation of OBSERVATION
+ * i (noise included: sd_i^2 is the latent variance + sn2); the standardised
+ * residual is (z_i - mu_i) / sd_i.
+ *   xyt, z, offs  the ragged batch, as oi_gpr_batch (a cell may be empty)
+ *   hyp    [ncell x 5] LINEAR (ell_x, ell_y, ell_t, sf2, sn2)
+ *   mu, sd [N]      in the observations' own order
+ *   lpl    [ncell]  or NULL: the log pseudo-likelihood; 0 for an empty cell
+ *   status [ncell]  0 ok, 1 the Cholesky failed: that cell's mu, sd and lpl
+ *                   are NaN
+ * n = 1 gives the prior: mu = mean, sd = sqrt(sf2 + sn2).  hyp, offs and all
+ * outputs are host arrays; with opts->device_inputs xyt and z are device
+ * pointers.  opts->stream, pool_bytes, max_pool and profile act as in
+ * oi_gpr_predict_multi; a cell's results depend neither on the other cells
+ * of the call nor on the chunking.  OI_E_ARG (before any device is touched):
+ * bad offs, a null pointer, a cell whose padded n x n matrix reaches 2 GiB.
+ * OI_E_NOMEM: a cell whose workspace (about 8 n^2 bytes) exceeds
+ * opts->pool_bytes (0 => 60% of the free HBM), with no output written. */
+int oi_gpr_loo(const double* xyt, const double* z, const int64_t* offs, int64_t ncell,
+               double mean, const double* hyp, double* mu, double* sd, double* lpl,
+               int32_t* status, const oi_options* opts);
+
+/* Leave-group-out prediction: every group of observations of a cell (a site,
+ * a pass, a day, a satellite) is predicted jointly from the cell's observations
+ * outside it, at given LINEAR hypers, from one factorisation per cell
+ * (Rasmussen & Williams, GPML 5.4.2, in block form):
+ *   r = z - mean, K~ = K + sn2 I, alpha = K~^-1 r, Q = K~^-1
+ * and for a group G of g observations, Q_GG = C C',
+ *   Sigma_G = Q_GG^-1           the predictive covariance of the group's
+ *                               OBSERVATIONS (noise included) given the others
+ *   mu_G = z_G - Q_GG^-1 alpha_G,  sd_i = sqrt([Q_GG^-1]_ii)
+ *   d2_G = alpha_G' Q_GG^-1 alpha_G        (chi^2 with g degrees under the model)
+ *   lpd_G = log N(z_G | mu_G, Sigma_G) = -d2_G / 2 + sum_k log C_kk - g log(2 pi) / 2
+ *   lpl = sum_G lpd_G
+ * A group of one is leave-one-out (oi_gpr_loo); a group that is the whole cell
+ * gives the prior: mu = mean, Sigma = K~.
+ *   xyt, z, offs  the ragged batch, as oi_gpr_batch (a cell may be empty)
+ *   group  [N]      the label of each observation.  Labels are compared only
+ *                   inside a cell and only for equality: any int64 is a label,
+ *                   and the same label in two cells means nothing.  Groups are
+ *                   taken in the order of their first appearance in the cell,
+ *                   members in observation order, so results depend on the
+ *                   partition and never on the label values.
+ *   hyp    [ncell x 5] LINEAR (ell_x, ell_y, ell_t, sf2, sn2)
+ *   mu, sd [N]      in the observations' own order
+ *   lpd, d2 [N]     or NULL: the value of the observation's group, repeated for
+ *                   every member
+ *   lpl    [ncell]  or NULL; 0 for an empty cell
+ *   status [ncell]  0 ok; 1 the cell's Cholesky failed: all of that cell's
+ *                   outputs are NaN; 2 some group's Q_GG failed to factor: those
+ *                   groups' rows and the cell's lpl are NaN, other groups' rows
+ *                   are valid
+ * n = 1 gives the prior: mu = mean, sd = sqrt(sf2 + sn2).  group, hyp, offs and
+ * all outputs are host arrays; with opts->device_inputs xyt and z are device
+ * pointers (group stays a host array).  opts->stream, pool_bytes, max_pool and
+ * profile act as in oi_gpr_loo; a cell's results depend neither on the other
+ * cells of the call nor on the chunking.  OI_E_ARG (before any device is
+ * touched): bad offs, a null pointer, a cell whose padded n x n matrix reaches
+ * 2 GiB.  OI_E_NOMEM: a cell whose workspace exceeds opts->pool_bytes (0 => 60%
+ * of the free HBM), with no output written; a cell needs oi_gpr_loo's
+ * workspace (about 8 n^2 bytes) plus, per group, 8 (gp^2 + 64 gp + (g + 1) g)
+ * bytes with gp = g rounded up to 64 -- about three times oi_gpr_loo's when the
+ * cell is one group. */
+int oi_gpr_lgo(const double* xyt, const double* z, const int64_t* offs, int64_t ncell,
+               const int64_t* group, double mean, const double* hyp, double* mu, double* sd,
+               double* lpd, double* d2, double* lpl, int32_t* status, const oi_options* opts);
+
+/* nsamp joint draws from every cell's GP posterior at the cell's own targets,
+ * at given LINEAR hypers.  Per cell, with fs and cov = Kxs - v'v exactly as
+ * oi_gpr_predict_multi forms them:
+ *   C = cov + (noise ? sn2 : 0) I + jitter I = Lc Lc'
+ *   samples[t, s] = fs[t] + sum_u Lc[t, u] Xi[u, s]
+ *   xyt, z, offs  the ragged batch, as oi_gpr_batch (a cell may be empty: the
+ *                 prior is drawn)
+ *   xs, toffs     targets [T x 3], cell c owning rows toffs[c] .. toffs[c + 1];
+ *                 T = toffs[ncell]; a cell may have none
+ *   hyp     [ncell x 5] LINEAR (ell_x, ell_y, ell_t, sf2, sn2)
+ *   nsamp   draws per cell, >= 0
+ *   noise   0: the latent field; 1: a new observation (sn2 on the diagonal)
+ *   jitter  >= 0, an absolute variance added to the diagonal of C
+ *   xi      NULL, or host [T x nsamp] standard normals, row toffs[c] + u and
+ *           column s holding Xi[u, s] of cell c: the deterministic mode
+ *   seed, streams  with xi == NULL, Xi is generated on the device by
+ *           Philox4x32-10 with key = (seed lo, seed hi): element e = s nt + u
+ *           of a cell comes from block b = e >> 1 with counter (b lo, b hi,
+ *           stream lo, stream hi); with the output words w0 .. w3,
+ *           u1 = (((w0 << 21) | (w1 >> 11)) + 1) 2^-53,
+ *           u2 = ((w2 << 21) | (w3 >> 11)) 2^-53, r = sqrt(-2 log u1),
+ *           theta = 2 pi u2; an even e is r cos theta, an odd e r sin theta.
+ *           streams [ncell] holds the cells' stream ids; NULL: the cell's index
+ *           in the call.  A cell's draws depend only on (seed, its stream, nt,
+ *           the columns asked for): the first S columns of a longer call are
+ *           the call with S draws.
+ *   samples [T x nsamp] row-major, rows aligned with fs and sd
+ *   fs, sd  [T] or NULL: bit for bit those of oi_gpr_predict_multi
+ *   status  [ncell]  0 ok; 1 the cell's Cholesky failed: fs, sd and samples
+ *           are NaN; 2 the factorisation of C met a pivot <= 0: samples are
+ *           NaN, fs and sd valid
+ * hyp, offs, toffs, xs, xi, streams and all outputs are host arrays; with
+ * opts->device_inputs xyt and z are device pointers.  opts->stream,
+ * pool_bytes, max_pool and profile act as in oi_gpr_predict_multi (stages
+ * ps_*); a cell's results depend neither on the other cells of the call nor on
+ * the chunking.  OI_E_ARG (before any device is touched): bad offs / toffs, a
+ * null required pointer, nsamp < 0, noise not 0 or 1, jitter negative or not
+ * finite, a cell whose K, X, padded C or nt nsamp reaches 2 GiB.  OI_E_NOMEM:
+ * a cell whose workspace exceeds opts->pool_bytes (0 => 60% of the free HBM),
+ * with no output written. */
+int oi_gpr_sample(const double* xyt, const double* z, const int64_t* offs, int64_t ncell,
+                  const double* xs, const int64_t* toffs, double mean, const double* hyp,
+                  int64_t nsamp, int32_t noise, double jitter,
+                  uint64_t seed, const uint64_t* streams, const double* xi,
+                  double* samples, double* fs, double* sd, int32_t* status,
+                  const oi_options* opts);
+
 /* ---- session: continuous batching across calls ------------------------
  * The per-cell loops GPR:258-261 / GPR:316-319 as a stream of batches: every
  * submitted batch (same arguments and semantics as oi_gpr_batch) joins one
@@ -225,9 +344,38 @@ int oi_nystrom_batch(const double* xyt, const double* y, const int64_t* offs, in
                      const double* xs, double mean, double* nlz, double* grad, double* pred,
                      int32_t* status, const oi_options* opts);
 
-/* The Nystrom prediction at many targets per cell with the posterior
- * covariance -- NB1 GPR(approx=True) with xs of size ns x 3 -- is declared in
- * its own header, include/oi_nystrom_multi.h. */
+/* NB1 GPR(x, y, xs, ell, sf2, sn2, mean, approx=True, M) with xs of size
+ * ns x 3: the Nystrom prediction at many targets per cell with the posterior
+ * covariance Kxs - Kxsx' Ki Kxsx that NB1 forms before taking its diagonal.
+ * The per-cell set-up (K_mm, eigh, the n x M panels, chol(B), W' = C L^-T, A)
+ * runs once per cell, not once per target.
+ *   xyt, y, offs, sel, soffs, hyp  as oi_nystrom_batch (LINEAR hypers, y the
+ *          residual outputs, 1 <= M <= n)
+ *   xs     [T x 3]  targets of all cells, cell c owning rows
+ *                   toffs[c] .. toffs[c+1]-1; no target (nt = 0) is valid
+ *   toffs  [ncell+1] target offsets, toffs[0] = 0, non-decreasing
+ *   fs     [T]      mean + Kxsx' A
+ *   sd     [T]      sqrt(diag(Kxs - err)), the root of the returned diagonal bit
+ *                   for bit; NaN where the argument is negative, as np.sqrt
+ *   cov    or NULL: Kxs - err, err = Kxsx'Kxsx / sn2 - (W Kxsx)'(W Kxsx); cell
+ *                   c's nt x nt matrix symmetric, row-major, at offset
+ *                   sum_{k<c} nt_k^2; Kxs has the diagonal sf2 exactly.  With
+ *                   NULL no nt x nt array exists anywhere and fs, sd are bitwise
+ *                   those of a call with cov
+ *   status [ncell]  0 ok, 1 eigh / Cholesky failed (NB1 LinAlgError): that
+ *                   cell's fs, sd and cov are NaN
+ * NB1's Nystrom err routinely exceeds Kxs: NaN entries of sd and a cov that is
+ * not positive semi-definite are the reference's results, with status 0.
+ * xs, toffs, hyp, sel, soffs and all outputs are host arrays; with
+ * opts->device_inputs xyt and y are device pointers.  A cell's results depend
+ * neither on the other cells of the call nor on its other targets.  A cell
+ * whose scratch (n x nt, M x nt, nt x nt) exceeds opts->pool_bytes (0 => 60%
+ * of the free HBM) is OI_E_NOMEM, with no output written. */
+int oi_nystrom_predict_multi(const double* xyt, const double* y, const int64_t* offs, int64_t ncell,
+                             const int64_t* sel, const int64_t* soffs, const double* hyp,
+                             const double* xs, const int64_t* toffs, double mean,
+                             double* fs, double* sd, double* cov, int32_t* status,
+                             const oi_options* opts);
 
 /* NB1 code cell 5 for a ragged batch: minimize(SMLII, x0, args=(x, y, True, M),
  * method='CG', jac=True) per cell (the restated scipy CG, maxiter <0 => 1000 =

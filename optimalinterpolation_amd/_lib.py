@@ -11,6 +11,7 @@ libamdhip64.so.7); streams handed over from torch are then valid here.
 import ctypes
 import os
 import threading
+import types
 
 import numpy as np
 
@@ -45,13 +46,16 @@ class OiError(RuntimeError):
 def _signatures():
     D, L, I = c_double_p, c_int64_p, c_int32_p
     f, l, i, u, n = ctypes.c_double, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int
-    H, S, O = ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(OiOptions)
+    H, S, O, U = ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(OiOptions), ctypes.POINTER(ctypes.c_uint64)
     fit = [D, D, L, l, L, L, D, D, f, D, I, I]   # the Nystrom fit's arguments up to info
     gpr = [D, D, L, l, D, f, D, i, D, D, I, I]   # oi_gpr_batch's arguments up to info
     return {
         'oi_options_default': (None, [O]),
         'oi_gpr_batch': (n, gpr + [O]),
         'oi_gpr_predict_multi': (n, [D, D, L, l, D, L, f, D, D, D, D, D, I, O]),
+        'oi_gpr_loo': (n, [D, D, L, l, f, D, D, D, D, I, O]),
+        'oi_gpr_lgo': (n, [D, D, L, l, L, f, D, D, D, D, D, D, I, O]),
+        'oi_gpr_sample': (n, [D, D, L, l, D, L, f, D, l, i, f, u, U, D, D, D, D, I, O]),
         'oi_nlml_grad_batch': (n, [D, D, D, L, l, D, D, D, I, O]),
         'oi_cg_create': (H, [D, f, i]),
         'oi_cg_step': (n, [H, D]),
@@ -66,6 +70,7 @@ def _signatures():
         'oi_ball_query': (n, [D, l, D, l, f, L, L, l, O]),
         'oi_gather_rows': (n, [D, D, D, D, l, L, l, D, D, O]),
         'oi_nystrom_batch': (n, [D, D, L, l, L, L, D, D, f, D, D, D, I, O]),
+        'oi_nystrom_predict_multi': (n, [D, D, L, l, L, L, D, D, L, f, D, D, D, I, O]),
         'oi_nystrom_fit_batch': (n, fit + [O]),
         'oi_svgp_param_count': (i, [i]),
         'oi_svgp_batch': (n, [D, D, L, l, D, i, D, i, i, i, u, f, D, D, D, D, I, O]),
@@ -84,42 +89,11 @@ def _signatures():
     }
 
 
-# name -> (restype, argtypes) of every symbol include/oi.h declares; load()
-# applies it and tests/test_abi.py compares it with the header's prototypes
+# name -> (restype, argtypes) of every symbol include/oi.h declares, the one
+# header and the one table; load() applies it and tests/test_abi.py compares it
+# with the header's prototypes
 SIGNATURES = _signatures()
 EXPORTS = tuple(SIGNATURES)
-
-# the same for include/oi_nystrom_multi.h, the header of the one entry point
-# that include/oi.h does not declare (tests/test_nystrom_predict_multi_abi.py
-# compares the two type by type)
-SIGNATURES_NYSTROM_MULTI = {
-    'oi_nystrom_predict_multi': (ctypes.c_int, [c_double_p, c_double_p, c_int64_p, ctypes.c_int64, c_int64_p,
-                                                c_int64_p, c_double_p, c_double_p, c_int64_p, ctypes.c_double,
-                                                c_double_p, c_double_p, c_double_p, c_int32_p,
-                                                ctypes.POINTER(OiOptions)]),
-}
-
-# and for include/oi_loo.h (tests/test_loo_abi.py)
-SIGNATURES_LOO = {
-    'oi_gpr_loo': (ctypes.c_int, [c_double_p, c_double_p, c_int64_p, ctypes.c_int64, ctypes.c_double,
-                                  c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
-                                  ctypes.POINTER(OiOptions)]),
-}
-
-# and for include/oi_lgo.h (tests/test_lgo_ref.py)
-SIGNATURES_LGO = {
-    'oi_gpr_lgo': (ctypes.c_int, [c_double_p, c_double_p, c_int64_p, ctypes.c_int64, c_int64_p, ctypes.c_double,
-                                  c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
-                                  c_int32_p, ctypes.POINTER(OiOptions)]),
-}
-
-# and for include/oi_sample.h (tests/test_sample_abi.py)
-SIGNATURES_SAMPLE = {
-    'oi_gpr_sample': (ctypes.c_int, [c_double_p, c_double_p, c_int64_p, ctypes.c_int64, c_double_p, c_int64_p,
-                                     ctypes.c_double, c_double_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
-                                     ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), c_double_p, c_double_p,
-                                     c_double_p, c_double_p, c_int32_p, ctypes.POINTER(OiOptions)]),
-}
 
 
 def load():
@@ -131,8 +105,7 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise OiError(f"{LIB_PATH} not built: run `make -C {_HERE}` (or __graft_entry__.build())")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in {**SIGNATURES, **SIGNATURES_NYSTROM_MULTI, **SIGNATURES_LOO,
-                                          **SIGNATURES_LGO, **SIGNATURES_SAMPLE}.items():
+        for name, (restype, argtypes) in SIGNATURES.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -270,6 +243,31 @@ def gpr_batch_device(xyt_dev, z_dev, offs, xs, mean, **kw):
     return gpr_batch(xyt_dev, z_dev, offs, xs, mean, device_inputs=True, **kw)
 
 
+def _dense_args(xyt, z, offs, hyp, device_inputs, opt_kw, xs=None, toffs=None):
+    """What gpr_predict_multi, gpr_loo, gpr_lgo and gpr_sample share, checked:
+    the ragged batch (and, with ``toffs``, its targets ``xs`` [T x 3]), ``hyp``
+    [ncell x 5], the observations' pointers, torch's current stream for device
+    inputs, the options and a zeroed status.  Returns them as one namespace;
+    ``head`` holds the C arguments every one of the four entries begins with."""
+    a = types.SimpleNamespace(offs=_i64(offs), xs=None, toffs=None)
+    a.ncell = len(a.offs) - 1
+    if toffs is not None:
+        a.toffs, a.xs = _i64(toffs), _f64(xs).reshape(-1, 3)
+        if len(a.toffs) != a.ncell + 1 or a.toffs[0] != 0 or a.toffs[-1] != a.xs.shape[0]:
+            raise ValueError("inconsistent ragged batch")
+    a.hyp = _f64(hyp).reshape(-1, 5)
+    if a.hyp.shape[0] != a.ncell:
+        raise ValueError("hyp must be [ncell x 5]")
+    dev = int(opt_kw.get('device', 0))
+    px, pz, a.keep = _obs(xyt, z, a.offs, device_inputs, dev, what='z')
+    if device_inputs:
+        opt_kw.setdefault('stream', _caller_stream(dev))
+    a.head = (px, pz, _ptr(a.offs, ctypes.c_int64), a.ncell)
+    a.opts = options(device_inputs=device_inputs, **opt_kw)
+    a.status = np.zeros(a.ncell, dtype=np.int32)
+    return a
+
+
 def gpr_predict_multi(xyt, z, offs, xs, toffs, mean, hyp, cov=False, lz=True, device_inputs=False,
                       **opt_kw):
     """oi_gpr_predict_multi: predict every cell at its own list of targets
@@ -280,31 +278,17 @@ def gpr_predict_multi(xyt, z, offs, xs, toffs, mean, hyp, cov=False, lz=True, de
     device_inputs=True ``xyt`` / ``z`` are fp64 contiguous torch tensors on
     cuda:``device`` and the call runs on torch's current stream; targets,
     offsets and hypers stay on the host."""
-    offs, toffs = _i64(offs), _i64(toffs)
-    xs = _f64(xs).reshape(-1, 3)
-    ncell = len(offs) - 1
-    if len(toffs) != ncell + 1 or toffs[0] != 0 or toffs[-1] != xs.shape[0]:
-        raise ValueError("inconsistent ragged batch")
-    hyp = _f64(hyp).reshape(-1, 5)
-    if hyp.shape[0] != ncell:
-        raise ValueError("hyp must be [ncell x 5]")
-    dev = int(opt_kw.get('device', 0))
-    px, pz, _keep = _obs(xyt, z, offs, device_inputs, dev, what='z')
-    if device_inputs:
-        opt_kw.setdefault('stream', _caller_stream(dev))
-    T = int(toffs[-1])
+    a = _dense_args(xyt, z, offs, hyp, device_inputs, opt_kw, xs, toffs)
+    T = int(a.toffs[-1])
     fs = np.empty(T)
     sd = np.empty(T)
-    lza = np.empty(ncell) if lz else None
-    nt = np.diff(toffs)
+    lza = np.empty(a.ncell) if lz else None
+    nt = np.diff(a.toffs)
     cova = np.empty(int((nt * nt).sum())) if cov else None
-    status = np.zeros(ncell, dtype=np.int32)
-    o = options(device_inputs=device_inputs, **opt_kw)
-    _check(load().oi_gpr_predict_multi(px, pz, _ptr(offs, ctypes.c_int64), ncell, _ptr(xs),
-                                       _ptr(toffs, ctypes.c_int64), float(mean), _ptr(hyp), _ptr(fs),
-                                       _ptr(sd), _ptr(lza), _ptr(cova), _ptr(status, ctypes.c_int32),
-                                       ctypes.byref(o)))
-    return fs, sd, lza, cova, status
+    _check(load().oi_gpr_predict_multi(*a.head, _ptr(a.xs), _ptr(a.toffs, ctypes.c_int64), float(mean), _ptr(a.hyp),
+                                       _ptr(fs), _ptr(sd), _ptr(lza), _ptr(cova), _ptr(a.status, ctypes.c_int32),
+                                       ctypes.byref(a.opts)))
+    return fs, sd, lza, cova, a.status
 
 
 def gpr_predict_multi_device(xyt_dev, z_dev, offs, xs, toffs, mean, hyp, **kw):
@@ -323,24 +307,14 @@ def gpr_loo(xyt, z, offs, mean, hyp, lpl=True, device_inputs=False, **opt_kw):
     results.  With device_inputs=True ``xyt`` / ``z`` are fp64 contiguous torch
     tensors on cuda:``device`` and the call runs on torch's current stream;
     offsets and hypers stay on the host."""
-    offs = _i64(offs)
-    ncell = len(offs) - 1
-    hyp = _f64(hyp).reshape(-1, 5)
-    if hyp.shape[0] != ncell:
-        raise ValueError("hyp must be [ncell x 5]")
-    dev = int(opt_kw.get('device', 0))
-    px, pz, _keep = _obs(xyt, z, offs, device_inputs, dev, what='z')
-    if device_inputs:
-        opt_kw.setdefault('stream', _caller_stream(dev))
-    N = int(offs[-1])
+    a = _dense_args(xyt, z, offs, hyp, device_inputs, opt_kw)
+    N = int(a.offs[-1])
     mu = np.empty(N)
     sd = np.empty(N)
-    lpla = np.empty(ncell) if lpl else None
-    status = np.zeros(ncell, dtype=np.int32)
-    o = options(device_inputs=device_inputs, **opt_kw)
-    _check(load().oi_gpr_loo(px, pz, _ptr(offs, ctypes.c_int64), ncell, float(mean), _ptr(hyp), _ptr(mu),
-                             _ptr(sd), _ptr(lpla), _ptr(status, ctypes.c_int32), ctypes.byref(o)))
-    return mu, sd, lpla, status
+    lpla = np.empty(a.ncell) if lpl else None
+    _check(load().oi_gpr_loo(*a.head, float(mean), _ptr(a.hyp), _ptr(mu), _ptr(sd), _ptr(lpla),
+                             _ptr(a.status, ctypes.c_int32), ctypes.byref(a.opts)))
+    return mu, sd, lpla, a.status
 
 
 def gpr_loo_device(xyt_dev, z_dev, offs, mean, hyp, **kw):
@@ -364,16 +338,8 @@ def gpr_lgo(xyt, z, offs, group, mean, hyp, lpd=True, d2=True, lpl=True, device_
     ``lpl`` NaN).  With device_inputs=True ``xyt`` / ``z`` are fp64 contiguous
     torch tensors on cuda:``device`` and the call runs on torch's current
     stream; labels, offsets and hypers stay on the host."""
-    offs = _i64(offs)
-    ncell = len(offs) - 1
-    hyp = _f64(hyp).reshape(-1, 5)
-    if hyp.shape[0] != ncell:
-        raise ValueError("hyp must be [ncell x 5]")
-    dev = int(opt_kw.get('device', 0))
-    px, pz, _keep = _obs(xyt, z, offs, device_inputs, dev, what='z')
-    if device_inputs:
-        opt_kw.setdefault('stream', _caller_stream(dev))
-    N = int(offs[-1])
+    a = _dense_args(xyt, z, offs, hyp, device_inputs, opt_kw)
+    N = int(a.offs[-1])
     group = _i64(group)
     if len(group) != N:
         raise ValueError("group must label every observation")
@@ -381,13 +347,11 @@ def gpr_lgo(xyt, z, offs, group, mean, hyp, lpd=True, d2=True, lpl=True, device_
     sd = np.empty(N)
     lpda = np.empty(N) if lpd else None
     d2a = np.empty(N) if d2 else None
-    lpla = np.empty(ncell) if lpl else None
-    status = np.zeros(ncell, dtype=np.int32)
-    o = options(device_inputs=device_inputs, **opt_kw)
-    _check(load().oi_gpr_lgo(px, pz, _ptr(offs, ctypes.c_int64), ncell, _ptr(group, ctypes.c_int64), float(mean),
-                             _ptr(hyp), _ptr(mu), _ptr(sd), _ptr(lpda), _ptr(d2a), _ptr(lpla),
-                             _ptr(status, ctypes.c_int32), ctypes.byref(o)))
-    return mu, sd, lpda, d2a, lpla, status
+    lpla = np.empty(a.ncell) if lpl else None
+    _check(load().oi_gpr_lgo(*a.head, _ptr(group, ctypes.c_int64), float(mean), _ptr(a.hyp), _ptr(mu), _ptr(sd),
+                             _ptr(lpda), _ptr(d2a), _ptr(lpla), _ptr(a.status, ctypes.c_int32),
+                             ctypes.byref(a.opts)))
+    return mu, sd, lpda, d2a, lpla, a.status
 
 
 def gpr_lgo_device(xyt_dev, z_dev, offs, group, mean, hyp, **kw):
@@ -414,40 +378,27 @@ def gpr_sample(xyt, z, offs, xs, toffs, mean, hyp, nsamp, noise=False, jitter=0.
     ``noise``).  With device_inputs=True ``xyt`` / ``z`` are fp64 contiguous
     torch tensors on cuda:``device`` and the call runs on torch's current
     stream; everything else stays on the host."""
-    offs, toffs = _i64(offs), _i64(toffs)
-    xs = _f64(xs).reshape(-1, 3)
-    ncell = len(offs) - 1
-    if len(toffs) != ncell + 1 or toffs[0] != 0 or toffs[-1] != xs.shape[0]:
-        raise ValueError("inconsistent ragged batch")
-    hyp = _f64(hyp).reshape(-1, 5)
-    if hyp.shape[0] != ncell:
-        raise ValueError("hyp must be [ncell x 5]")
+    a = _dense_args(xyt, z, offs, hyp, device_inputs, opt_kw, xs, toffs)
     nsamp = int(nsamp)
     if nsamp < 0:
         raise ValueError("nsamp must be >= 0")
-    T = int(toffs[-1])
+    T = int(a.toffs[-1])
     if streams is not None:
         streams = np.ascontiguousarray(streams, dtype=np.uint64).reshape(-1)
-        if len(streams) != ncell:
+        if len(streams) != a.ncell:
             raise ValueError("streams must be [ncell]")
     if xi is not None:
         xi = _f64(xi)
         if xi.size != T * nsamp:
             raise ValueError("xi must be [T x nsamp]")
-    dev = int(opt_kw.get('device', 0))
-    px, pz, _keep = _obs(xyt, z, offs, device_inputs, dev, what='z')
-    if device_inputs:
-        opt_kw.setdefault('stream', _caller_stream(dev))
     samples = np.empty((T, nsamp))
     fs = np.empty(T)
     sd = np.empty(T)
-    status = np.zeros(ncell, dtype=np.int32)
-    o = options(device_inputs=device_inputs, **opt_kw)
-    _check(load().oi_gpr_sample(px, pz, _ptr(offs, ctypes.c_int64), ncell, _ptr(xs), _ptr(toffs, ctypes.c_int64),
-                                float(mean), _ptr(hyp), nsamp, 1 if noise else 0, float(jitter),
-                                int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(streams, ctypes.c_uint64), _ptr(xi),
-                                _ptr(samples), _ptr(fs), _ptr(sd), _ptr(status, ctypes.c_int32), ctypes.byref(o)))
-    return samples, fs, sd, status
+    _check(load().oi_gpr_sample(*a.head, _ptr(a.xs), _ptr(a.toffs, ctypes.c_int64), float(mean), _ptr(a.hyp), nsamp,
+                                1 if noise else 0, float(jitter), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                _ptr(streams, ctypes.c_uint64), _ptr(xi), _ptr(samples), _ptr(fs), _ptr(sd),
+                                _ptr(a.status, ctypes.c_int32), ctypes.byref(a.opts)))
+    return samples, fs, sd, a.status
 
 
 def gpr_sample_device(xyt_dev, z_dev, offs, xs, toffs, mean, hyp, nsamp, **kw):

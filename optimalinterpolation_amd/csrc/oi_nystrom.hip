@@ -49,7 +49,6 @@
 #include <string>
 #include <vector>
 
-#include "../../include/oi_nystrom_multi.h"
 #include "oi_gemm.h"
 #include "oi_host.h"
 #include "oi_linalg.h"

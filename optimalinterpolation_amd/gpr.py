@@ -128,6 +128,17 @@ def gpr_cells(cells, opt=True, x0=None, hyp=None, info=False, **kw):
                           hyp=hyp, info=info, **o)
 
 
+def _fit_then(cells, opt, x0, hyp, kw):
+    """The four functions below begin so: (the module's options merged with
+    ``kw`` for their own liboi call, ``gpr_cells``' out8 and status under the
+    caller's ``kw``, the hypers [ncell x 5] to go on with)."""
+    o = dict(options)
+    o.update(kw)
+    out8, status, _ = gpr_cells(cells, opt=opt, x0=x0, hyp=hyp, **kw)
+    h = out8[:, 3:8] if opt else np.asarray(hyp, dtype=np.float64).reshape(-1, 5)
+    return o, out8, status, h
+
+
 def gpr_cells_multi(cells, xs, toffs, opt=True, x0=None, hyp=None, cov=False, **kw):
     """Predict every cell of a RaggedCells object at a list of targets of its
     own -- the notebook's ``GPR(x, y, xs, ...)`` with ``xs`` ns x 3 -- with the
@@ -142,10 +153,7 @@ def gpr_cells_multi(cells, xs, toffs, opt=True, x0=None, hyp=None, cov=False, **
     ``cells.xs`` (fs, sd, lZ, hypers), ``cov_list[c]`` the nt_c x nt_c matrix of
     cell c, ``status[c]`` non-zero where the fit's or the prediction's
     covariance was not positive definite (NaN outputs)."""
-    o = dict(options)
-    o.update(kw)
-    out8, status, _ = gpr_cells(cells, opt=opt, x0=x0, hyp=hyp, **kw)
-    h = out8[:, 3:8] if opt else np.asarray(hyp, dtype=np.float64).reshape(-1, 5)
+    o, out8, status, h = _fit_then(cells, opt, x0, hyp, kw)
     fs, sd, _, cv, st = _lib.gpr_predict_multi(cells.xyt, cells.z, cells.offs, xs, toffs, cells.mean,
                                                h, cov=cov, lz=False, **o)
     return fs, sd, (_lib.split_cov(cv, toffs) if cov else None), out8, np.maximum(status, st)
@@ -164,10 +172,7 @@ def loo_cells(cells, opt=True, x0=None, hyp=None, **kw):
     pseudo-likelihood per cell, ``out8`` what ``gpr_cells`` returns, and
     ``status[c]`` the maximum of the fit's and the cross-validation's (non-zero:
     a covariance was not positive definite, NaN outputs)."""
-    o = dict(options)
-    o.update(kw)
-    out8, status, _ = gpr_cells(cells, opt=opt, x0=x0, hyp=hyp, **kw)
-    h = out8[:, 3:8] if opt else np.asarray(hyp, dtype=np.float64).reshape(-1, 5)
+    o, out8, status, h = _fit_then(cells, opt, x0, hyp, kw)
     mu, sd, lpl, st = _lib.gpr_loo(cells.xyt, cells.z, cells.offs, cells.mean, h, **o)
     return mu, sd, lpl, out8, np.maximum(status, st)
 
@@ -187,10 +192,7 @@ def lgo_cells(cells, group, opt=True, x0=None, hyp=None, **kw):
     the model) of i's group, repeated for every member; ``lpl`` sums ``lpd`` over
     a cell's groups; ``status[c]`` is the maximum of the fit's and the
     cross-validation's."""
-    o = dict(options)
-    o.update(kw)
-    out8, status, _ = gpr_cells(cells, opt=opt, x0=x0, hyp=hyp, **kw)
-    h = out8[:, 3:8] if opt else np.asarray(hyp, dtype=np.float64).reshape(-1, 5)
+    o, out8, status, h = _fit_then(cells, opt, x0, hyp, kw)
     mu, sd, lpd, d2, lpl, st = _lib.gpr_lgo(cells.xyt, cells.z, cells.offs, group, cells.mean, h, **o)
     return mu, sd, lpd, d2, lpl, out8, np.maximum(status, st)
 
@@ -211,10 +213,7 @@ def sample_cells(cells, xs, toffs, nsamp, opt=True, x0=None, hyp=None, **kw):
     ``gpr_predict_multi``'s, ``out8`` is what ``gpr_cells`` returns, and
     ``status[c]`` the maximum of the fit's and the draw's."""
     draw = {k: kw.pop(k) for k in ('noise', 'jitter', 'seed', 'streams', 'xi') if k in kw}
-    o = dict(options)
-    o.update(kw)
-    out8, status, _ = gpr_cells(cells, opt=opt, x0=x0, hyp=hyp, **kw)
-    h = out8[:, 3:8] if opt else np.asarray(hyp, dtype=np.float64).reshape(-1, 5)
+    o, out8, status, h = _fit_then(cells, opt, x0, hyp, kw)
     samples, fs, sd, st = _lib.gpr_sample(cells.xyt, cells.z, cells.offs, xs, toffs, cells.mean, h, nsamp,
                                           **draw, **o)
     return samples, fs, sd, out8, np.maximum(status, st)

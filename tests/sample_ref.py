@@ -1,5 +1,5 @@
 """Joint posterior draws of one cell in plain numpy: the reference of
-``oi_gpr_sample`` (include/oi_sample.h; tests/test_gpu_sample.py).
+``oi_gpr_sample`` (include/oi.h; tests/test_gpu_sample.py).
 
 ``philox4x32_10`` restates the counter-based generator (Salmon et al., SC'11),
 ``normals`` the header's mapping from (seed, stream, element) to a standard

@@ -3,19 +3,17 @@ CPU only: no compute entry point is called here."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_ref
+from abi_ref import _ctype
 from conftest import ROOT
 from optimalinterpolation_amd import _lib
 
-HEADER = os.path.join(ROOT, 'include', 'oi.h')
-
-
 def declared():
-    src = open(HEADER).read()
+    src = open(abi_ref.HEADER).read()
     src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
     return sorted(set(re.findall(r'\b(oi_[a-z0-9_]+)\s*\(', src)))
 
@@ -24,33 +22,14 @@ def test_header_matches_binding_list():
     assert declared() == sorted(_lib.EXPORTS)
 
 
-def _ctype(decl):
-    """The ctypes type of a C type as include/oi.h spells it."""
-    t = re.sub(r'\s+', ' ', re.sub(r'\bconst\b', '', decl)).strip().replace(' *', '*')
-    scalar = {'double': ctypes.c_double, 'int64_t': ctypes.c_int64, 'int32_t': ctypes.c_int32,
-              'uint64_t': ctypes.c_uint64, 'int': ctypes.c_int}
-    if t in scalar:
-        return scalar[t]
-    if t.endswith('*') and t[:-1] in scalar:
-        return ctypes.POINTER(scalar[t[:-1]])
-    if t in ('void', 'void*', 'char*'):
-        return {'void': None, 'void*': ctypes.c_void_p, 'char*': ctypes.c_char_p}[t]
-    if t == 'oi_options*':
-        return ctypes.POINTER(_lib.OiOptions)
-    assert re.fullmatch(r'(struct )?oi_\w+\*', t), f"unmapped C type {decl!r}"
-    return ctypes.c_void_p    # an opaque handle
-
-
 def test_binding_types_match_the_header():
     """Every prototype of include/oi.h against _lib.SIGNATURES (which load()
     applies), and struct oi_options against OiOptions, type by type."""
-    src = re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S))
-    protos = re.findall(r'([A-Za-z_][\w\s\*]*?)\b(oi_[a-z0-9_]+)\s*\(([^)]*)\)\s*;', src)
-    assert len(protos) == 32 and sorted(n for _, n, _ in protos) == sorted(_lib.SIGNATURES)
+    src, protos = abi_ref.source(), abi_ref.protos()
+    assert len(protos) == 36 and sorted(n for _, n, _ in protos) == sorted(_lib.SIGNATURES)
     lib = _lib.load()
     for ret, name, args in protos:
-        args = [a.strip() for a in args.split(',')] if args.strip() not in ('', 'void') else []
-        want = [_ctype(re.match(r'(.*?)\w+$', a).group(1)) for a in args]
+        want = [_ctype(a) for a in args]
         restype, argtypes = _lib.SIGNATURES[name]
         assert (restype, list(argtypes)) == (_ctype(ret), want), name
         fn = getattr(lib, name)
@@ -64,10 +43,7 @@ def test_library_exports_every_symbol():
     lib = _lib.load()
     for name in declared():
         assert hasattr(lib, name), name
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True,
-                         text=True, check=True).stdout
-    exported = set(re.findall(r'\b[TW] (oi_\w+)', out))
-    assert set(declared()) <= exported
+    assert set(declared()) <= abi_ref.exported()
 
 
 def test_version_and_options_defaults():

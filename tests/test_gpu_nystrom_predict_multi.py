@@ -1,5 +1,5 @@
 """GPU tests of ``oi_nystrom_predict_multi``: NB1 GPR(approx=True) at many
-targets per cell with the posterior covariance (include/oi_nystrom_multi.h).
+targets per cell with the posterior covariance (include/oi.h).
 
 Reference: the oracle's own functions (nystrom_multi_cases.reference):
   Ki, A = nystroem(...);  k = matern32(x, xs=xs)

@@ -1,5 +1,5 @@
 """GPU parity of ``oi_gpr_sample``: joint posterior draws per cell
-(include/oi_sample.h), against tests/sample_ref.py.
+(include/oi.h), against tests/sample_ref.py.
 
 Bounds, fixed before any GPU run:
   samples  |gpu - ref| <= 1e-10 * max(sqrt(sf2), |ref|)   (the project's T1 scaled to the draw)

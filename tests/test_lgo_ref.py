@@ -1,18 +1,15 @@
-"""``oi_gpr_lgo`` (include/oi_lgo.h) without a GPU: the two numpy references of
+"""``oi_gpr_lgo`` without a GPU: the two numpy references of
 tests/lgo_ref.py agree on every input of tests/test_gpu_lgo.py, the library's
 host plan and workspace count equal their Python restatements, the symbol is
-exported and bound type by type, ``gpr.site_groups`` joins exactly the repeated
+declared, exported and bound, ``gpr.site_groups`` joins exactly the repeated
 sites, and every misuse is rejected with OI_E_ARG (-1) before any device work.
 """
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import abi_ref
 from optimalinterpolation_amd import _lib, gpr, nystrom
 import lgo_ref as R
 
@@ -141,41 +138,9 @@ def test_site_groups_joins_bitwise_equal_rows_per_cell():
 
 # -- the ABI ------------------------------------------------------------------------
 
-def _ctype(decl):
-    t = re.sub(r'\s+', ' ', re.sub(r'\bconst\b', '', decl)).strip().replace(' *', '*')
-    scalar = {'double': ctypes.c_double, 'int64_t': ctypes.c_int64, 'int32_t': ctypes.c_int32, 'int': ctypes.c_int}
-    if t in scalar:
-        return scalar[t]
-    if t.endswith('*') and t[:-1] in scalar:
-        return ctypes.POINTER(scalar[t[:-1]])
-    assert t == 'oi_options*', f"unmapped C type {decl!r}"
-    return ctypes.POINTER(_lib.OiOptions)
-
-
-def _protos(header):
-    src = open(os.path.join(ROOT, 'include', header)).read()
-    src = re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', src, flags=re.S))
-    return re.findall(r'([A-Za-z_][\w\s\*]*?)\b(oi_[a-z0-9_]+)\s*\(([^)]*)\)\s*;', src)
-
-
 def test_symbol_exported_and_bound():
-    protos = _protos('oi_lgo.h')
-    assert [n for _, n, _ in protos] == ['oi_gpr_lgo'] == list(_lib.SIGNATURES_LGO)
-    assert not set(_lib.SIGNATURES_LGO) & (set(_lib.SIGNATURES) | set(_lib.SIGNATURES_NYSTROM_MULTI)
-                                           | set(_lib.SIGNATURES_LOO))
-    lib = _lib.load()
-    for ret, name, args in protos:
-        want = [_ctype(re.match(r'(.*?)\w+$', a.strip()).group(1)) for a in args.split(',')]
-        restype, argtypes = _lib.SIGNATURES_LGO[name]
-        ret = ret.strip().splitlines()[-1]
-        assert (restype, list(argtypes)) == (_ctype(ret), want)
-        fn = getattr(lib, name)
-        assert (fn.restype, list(fn.argtypes)) == (restype, list(argtypes)) and len(argtypes) == 14
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True,
-                         check=True).stdout
-    for sym in ('oi_gpr_lgo', 'oi_test_lgo_plan', 'oi_test_lgo_cell_doubles'):
-        assert re.search(rf'\b[TW] {sym}\b', out)
-    assert 'oi_gpr_lgo' not in [n for _, n, _ in _protos('oi.h')] and len(_protos('oi.h')) == 32
+    assert 'oi_gpr_lgo' in _lib.SIGNATURES and abi_ref.nargs('oi_gpr_lgo') == 14 == len(_lib.SIGNATURES['oi_gpr_lgo'][1])
+    assert {'oi_gpr_lgo', 'oi_test_lgo_plan', 'oi_test_lgo_cell_doubles'} <= abi_ref.exported()
     assert callable(_lib.gpr_lgo) and callable(_lib.gpr_lgo_device)
     assert callable(gpr.lgo_cells) and callable(gpr.site_groups) and callable(nystrom.GPR_lgo)
 

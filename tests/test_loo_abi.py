@@ -1,37 +1,16 @@
-"""``oi_gpr_loo`` (include/oi_loo.h) without a GPU: the symbol is exported and
-bound type by type, include/oi.h keeps its 32 prototypes, and every misuse is
+"""``oi_gpr_loo`` without a GPU: the symbol is declared, exported and bound
+(tests/test_abi.py compares its types with include/oi.h), and every misuse is
 rejected with OI_E_ARG (-1) and a message before any device work -- as
 tests/test_nystrom_predict_multi_abi.py checks for its entry point."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import abi_ref
 from optimalinterpolation_amd import _lib, gpr, nystrom
 
 D, I64, I32 = ctypes.c_double, ctypes.c_int64, ctypes.c_int32
-
-
-def _ctype(decl):
-    """The ctypes type of a C type as the header spells it."""
-    t = re.sub(r'\s+', ' ', re.sub(r'\bconst\b', '', decl)).strip().replace(' *', '*')
-    scalar = {'double': ctypes.c_double, 'int64_t': ctypes.c_int64, 'int32_t': ctypes.c_int32, 'int': ctypes.c_int}
-    if t in scalar:
-        return scalar[t]
-    if t.endswith('*') and t[:-1] in scalar:
-        return ctypes.POINTER(scalar[t[:-1]])
-    assert t == 'oi_options*', f"unmapped C type {decl!r}"
-    return ctypes.POINTER(_lib.OiOptions)
-
-
-def _protos(header):
-    src = open(os.path.join(ROOT, 'include', header)).read()
-    src = re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', src, flags=re.S))
-    return re.findall(r'([A-Za-z_][\w\s\*]*?)\b(oi_[a-z0-9_]+)\s*\(([^)]*)\)\s*;', src)
 
 
 def _p(a, t):
@@ -52,27 +31,10 @@ def _call(lib, **over):
 
 
 def test_symbol_exported_and_bound():
-    protos = _protos('oi_loo.h')
-    assert [n for _, n, _ in protos] == ['oi_gpr_loo'] == list(_lib.SIGNATURES_LOO)
-    assert not set(_lib.SIGNATURES_LOO) & (set(_lib.SIGNATURES) | set(_lib.SIGNATURES_NYSTROM_MULTI))
-    lib = _lib.load()
-    for ret, name, args in protos:
-        want = [_ctype(re.match(r'(.*?)\w+$', a.strip()).group(1)) for a in args.split(',')]
-        restype, argtypes = _lib.SIGNATURES_LOO[name]
-        ret = ret.strip().splitlines()[-1]    # the pattern's first group starts at the preceding #endif
-        assert (restype, list(argtypes)) == (_ctype(ret), want)
-        fn = getattr(lib, name)
-        assert (fn.restype, list(fn.argtypes)) == (restype, list(argtypes)) and len(argtypes) == 11
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True,
-                         check=True).stdout
-    assert re.search(r'\b[TW] oi_gpr_loo\b', out)
+    assert 'oi_gpr_loo' in _lib.SIGNATURES and abi_ref.nargs('oi_gpr_loo') == 11 == len(_lib.SIGNATURES['oi_gpr_loo'][1])
+    assert 'oi_gpr_loo' in abi_ref.exported()
     assert callable(_lib.gpr_loo) and callable(_lib.gpr_loo_device)
     assert callable(gpr.loo_cells) and callable(nystrom.GPR_loo)
-
-
-def test_oi_h_keeps_its_32_prototypes():
-    names = [n for _, n, _ in _protos('oi.h')]
-    assert len(names) == 32 and 'oi_gpr_loo' not in names
 
 
 @pytest.mark.parametrize('over, word', [

@@ -1,31 +1,16 @@
-"""``oi_nystrom_predict_multi`` (include/oi_nystrom_multi.h) without a GPU: the symbol is
+"""``oi_nystrom_predict_multi`` without a GPU: the symbol is declared,
 exported and bound, and every misuse is rejected with OI_E_ARG (-1) and a
 message before any device work -- as tests/test_predict_multi_abi.py checks for
 ``oi_gpr_predict_multi``."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import abi_ref
 from optimalinterpolation_amd import _lib, nystrom
 
 D, I64, I32 = ctypes.c_double, ctypes.c_int64, ctypes.c_int32
-
-
-def _ctype(decl):
-    """The ctypes type of a C type as the header spells it."""
-    t = re.sub(r'\s+', ' ', re.sub(r'\bconst\b', '', decl)).strip().replace(' *', '*')
-    scalar = {'double': ctypes.c_double, 'int64_t': ctypes.c_int64, 'int32_t': ctypes.c_int32, 'int': ctypes.c_int}
-    if t in scalar:
-        return scalar[t]
-    if t.endswith('*') and t[:-1] in scalar:
-        return ctypes.POINTER(scalar[t[:-1]])
-    assert t == 'oi_options*', f"unmapped C type {decl!r}"
-    return ctypes.POINTER(_lib.OiOptions)
 
 
 def _p(a, t):
@@ -50,27 +35,11 @@ def _call(lib, **over):
 
 
 def test_symbol_exported_and_bound():
-    """The entry point is declared in include/oi_nystrom_multi.h (include/oi.h's
-    list of prototypes is pinned by tests/test_abi.py) and bound from
-    _lib.SIGNATURES_NYSTROM_MULTI: the same checks as tests/test_abi.py makes
-    for include/oi.h -- header and table name the same symbols, the types agree
-    one by one, load() applies them and the library exports the symbol."""
-    src = open(os.path.join(ROOT, 'include', 'oi_nystrom_multi.h')).read()
-    src = re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', src, flags=re.S))
-    protos = re.findall(r'([A-Za-z_][\w\s\*]*?)\b(oi_[a-z0-9_]+)\s*\(([^)]*)\)\s*;', src)
-    assert [n for _, n, _ in protos] == ['oi_nystrom_predict_multi'] == list(_lib.SIGNATURES_NYSTROM_MULTI)
-    assert not set(_lib.SIGNATURES_NYSTROM_MULTI) & set(_lib.SIGNATURES)
-    lib = _lib.load()
-    for ret, name, args in protos:
-        want = [_ctype(re.match(r'(.*?)\w+$', a.strip()).group(1)) for a in args.split(',')]
-        restype, argtypes = _lib.SIGNATURES_NYSTROM_MULTI[name]
-        ret = ret.strip().splitlines()[-1]    # the pattern's first group starts at the preceding #endif
-        assert (restype, list(argtypes)) == (_ctype(ret), want)
-        fn = getattr(lib, name)
-        assert (fn.restype, list(fn.argtypes)) == (restype, list(argtypes)) and len(argtypes) == 15
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True,
-                         check=True).stdout
-    assert re.search(r'\b[TW] oi_nystrom_predict_multi\b', out)
+    """The entry point is declared in include/oi.h with 15 arguments, is in
+    _lib.SIGNATURES (tests/test_abi.py compares the two type by type) and is
+    exported by the library."""
+    assert 'oi_nystrom_predict_multi' in _lib.SIGNATURES and abi_ref.nargs('oi_nystrom_predict_multi') == 15 == len(_lib.SIGNATURES['oi_nystrom_predict_multi'][1])
+    assert 'oi_nystrom_predict_multi' in abi_ref.exported()
     assert callable(_lib.nystrom_predict_multi)
     for name in ('GPR_multi', 'GPR_multi_batch', 'fit_predict_multi_batch'):
         assert callable(getattr(nystrom, name))

@@ -1,38 +1,17 @@
-"""``oi_gpr_sample`` (include/oi_sample.h) without a GPU: the symbol is exported
-and bound type by type, the other signature tables do not know it, every misuse
-is rejected with OI_E_ARG (-1) and a message before any device work, and the
+"""``oi_gpr_sample`` without a GPU: the symbol is declared, exported and bound
+(tests/test_abi.py compares its types with include/oi.h), every misuse is
+rejected with OI_E_ARG (-1) and a message before any device work, and the
 workspace the chunk planner counts for a cell equals the layout restated here
 -- as tests/test_loo_abi.py checks for its entry point."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import abi_ref
 from optimalinterpolation_amd import _lib, gpr, nystrom
 
 D, I64, I32, U64 = ctypes.c_double, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64
-
-
-def _ctype(decl):
-    """The ctypes type of a C type as the header spells it."""
-    t = re.sub(r'\s+', ' ', re.sub(r'\bconst\b', '', decl)).strip().replace(' *', '*')
-    scalar = {'double': D, 'int64_t': I64, 'int32_t': I32, 'uint64_t': U64, 'int': ctypes.c_int}
-    if t in scalar:
-        return scalar[t]
-    if t.endswith('*') and t[:-1] in scalar:
-        return ctypes.POINTER(scalar[t[:-1]])
-    assert t == 'oi_options*', f"unmapped C type {decl!r}"
-    return ctypes.POINTER(_lib.OiOptions)
-
-
-def _protos(header):
-    src = open(os.path.join(ROOT, 'include', header)).read()
-    src = re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', src, flags=re.S))
-    return re.findall(r'([A-Za-z_][\w\s\*]*?)\b(oi_[a-z0-9_]+)\s*\(([^)]*)\)\s*;', src)
 
 
 def _p(a, t):
@@ -56,30 +35,10 @@ def _call(lib, **over):
 
 
 def test_symbol_exported_and_bound():
-    protos = _protos('oi_sample.h')
-    assert [n for _, n, _ in protos] == ['oi_gpr_sample'] == list(_lib.SIGNATURES_SAMPLE)
-    others = (set(_lib.SIGNATURES) | set(_lib.SIGNATURES_NYSTROM_MULTI) | set(_lib.SIGNATURES_LOO)
-              | set(_lib.SIGNATURES_LGO))
-    assert not set(_lib.SIGNATURES_SAMPLE) & others
-    lib = _lib.load()
-    for ret, name, args in protos:
-        want = [_ctype(re.match(r'(.*?)\w+$', a.strip()).group(1)) for a in args.split(',')]
-        restype, argtypes = _lib.SIGNATURES_SAMPLE[name]
-        ret = ret.strip().splitlines()[-1]    # the pattern's first group starts at the preceding #endif
-        assert (restype, list(argtypes)) == (_ctype(ret), want)
-        fn = getattr(lib, name)
-        assert (fn.restype, list(fn.argtypes)) == (restype, list(argtypes)) and len(argtypes) == 19
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True,
-                         check=True).stdout
-    assert re.search(r'\b[TW] oi_gpr_sample\b', out)
-    assert re.search(r'\b[TW] oi_test_sample_normals\b', out) and re.search(r'\b[TW] oi_test_sample_cell_doubles\b', out)
+    assert 'oi_gpr_sample' in _lib.SIGNATURES and abi_ref.nargs('oi_gpr_sample') == 19 == len(_lib.SIGNATURES['oi_gpr_sample'][1])
+    assert {'oi_gpr_sample', 'oi_test_sample_normals', 'oi_test_sample_cell_doubles'} <= abi_ref.exported()
     assert callable(_lib.gpr_sample) and callable(_lib.gpr_sample_device)
     assert callable(gpr.sample_cells) and callable(nystrom.GPR_sample)
-
-
-def test_oi_h_keeps_its_32_prototypes():
-    names = [n for _, n, _ in _protos('oi.h')]
-    assert len(names) == 32 and 'oi_gpr_sample' not in names
 
 
 @pytest.mark.parametrize('over, word', [

@@ -9,6 +9,14 @@ must not change a single bit).  One small case per entry family:
   prediction    gpr_predict_multi with the covariance, n and nt around the
                 64-tile, in one chunk and in several
   leave-one-out gpr_loo with lpl, n around the 64-tile, in one chunk and in several
+  leave-group-out gpr_lgo with lpd, d2 and lpl, n around the 64-tile under four
+                labellings (singletons, a group across the tile boundary, one
+                whole-cell group, interleaved), in one chunk, in several and on
+                device tensors
+  sampling      gpr_sample at nt around the 64-tile and 0, 1 and 3 draws: the
+                device generator with given and with default streams, the
+                caller's normals, noise, jitter, a covariance that does not
+                factor (status 2); in one chunk and in several
   Nystrom multi nystrom_predict_multi without and with the covariance, n, M and
                 nt around the 64-tile
   SVGP          a short Adam run with logging; predict_f with the covariance
@@ -130,6 +138,57 @@ def _loo(_lib, synthetic):
                 loo_stage_names=names, loo_stage_launches=launches)
 
 
+def _lgo(_lib, synthetic):
+    ns = [1, 63, 64, 65, 130]
+
+    def straddle(n):  # rows 60..69 are one group: behind 60 singletons it lies across rows 64
+        lab = np.arange(n)
+        lab[60:70] = 60
+        return lab
+    kinds = [np.arange, straddle, lambda n: np.zeros(n, dtype=np.int64), lambda n: np.arange(n) % 3]
+    sizes = [n for _ in kinds for n in ns]
+    c = synthetic.make_cells(sizes, seed=17)
+    lab = np.concatenate([k(n) for k in kinds for n in ns])
+    hyp = np.tile(synthetic.FIXED_HYPERS, (len(sizes), 1))
+    args = (c.offs, lab, c.mean, hyp)
+    keys = ('mu', 'sd', 'lpd', 'd2', 'lpl', 'st')
+    r = {}
+    for tag, res in (('', _lib.gpr_lgo(c.xyt, c.z, *args)), ('2', _lib.gpr_lgo(c.xyt, c.z, *args, max_pool=2)),
+                     ('_dev', _lib.gpr_lgo(*_cuda(c.xyt, c.z), *args, device_inputs=True))):
+        r.update({f'lgo_{k}{tag}': v for k, v in zip(keys, res)})
+    _lib.profile_reset()
+    _lib.gpr_lgo(c.xyt, c.z, *args, max_pool=2, profile=True)
+    names, launches = _stages(_lib, 'lgo_')
+    assert launches.max() >= 2, "max_pool did not force a second chunk"
+    return dict(r, lgo_stage_names=names, lgo_stage_launches=launches)
+
+
+def _sample(_lib, synthetic):
+    sizes, nts = [63, 64, 65, 64, 64], [0, 1, 64, 65, 2]
+    c = synthetic.make_cells(sizes, seed=19)
+    rng = np.random.default_rng(20)
+    toffs = np.concatenate([[0], np.cumsum(nts)])
+    xs = np.repeat(c.xs, nts, axis=0) + rng.normal(0, 1.0, (toffs[-1], 3)) * [5e4, 5e4, 1.0]
+    xs[-1] = xs[-2]  # the last cell's two targets coincide: its latent covariance does not factor
+    hyp = np.tile(synthetic.FIXED_HYPERS, (len(sizes), 1))
+    args = (c.xyt, c.z, c.offs, xs, toffs, c.mean, hyp)
+    streams = np.array([7, 2 ** 63 + 5, 0, 2 ** 32, 11], dtype=np.uint64)
+    r = {}
+    for nsamp in (0, 1, 3):
+        xi = rng.standard_normal((toffs[-1], nsamp))
+        for tag, kw in (('rng', dict(seed=3)), ('streams', dict(seed=3, streams=streams)), ('xi', dict(xi=xi)),
+                        ('noise', dict(seed=3, noise=True)), ('jitter', dict(seed=3, jitter=1e-6))):
+            for ctag, ckw in (('', {}), ('_chunked', dict(max_pool=2))):
+                res = _lib.gpr_sample(*args, nsamp, **kw, **ckw)
+                r.update({f'ps_{k}_{tag}{nsamp}{ctag}': v for k, v in zip(('samples', 'fs', 'sd', 'st'), res)})
+    assert r['ps_st_rng3'][-1] == 2 and r['ps_st_noise3'][-1] == 0, "the duplicated target did not give status 2"
+    _lib.profile_reset()
+    _lib.gpr_sample(*args, 3, seed=3, max_pool=2, profile=True)
+    names, launches = _stages(_lib, 'ps_')
+    assert launches.max() >= 2, "max_pool did not force a second chunk"
+    return dict(r, ps_stage_names=names, ps_stage_launches=launches)
+
+
 def _nystrom_multi(_lib, synthetic):
     from optimalinterpolation_amd import nystrom
     ns, Ms, nts = [70, 130, 200, 260], np.array([20, 33, 64, 65]), [1, 64, 65, 130]
@@ -207,6 +266,8 @@ def run(out):
     r.update(_nystrom(_lib, synthetic))
     r.update(_predict(_lib, synthetic))
     r.update(_loo(_lib, synthetic))
+    r.update(_lgo(_lib, synthetic))
+    r.update(_sample(_lib, synthetic))
     r.update(_nystrom_multi(_lib, synthetic))
     r.update(_svgp(_lib))
     r.update(_day(_lib))
