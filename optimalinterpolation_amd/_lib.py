@@ -96,6 +96,19 @@ SIGNATURES = _signatures()
 EXPORTS = tuple(SIGNATURES)
 
 
+def _ext_signatures():
+    D, L, I, O = c_double_p, c_int64_p, c_int32_p, ctypes.POINTER(OiOptions)
+    f, l, n = ctypes.c_double, ctypes.c_int64, ctypes.c_int
+    return {
+        'oi_gpr_predict_grad': (n, [D, D, L, l, D, L, f, D, D, D, D, D, D, D, I, O]),
+    }
+
+
+# the same for include/oi_ext.h, where the entries after oi.h's are declared
+# (tests/test_grad_abi.py compares it with that header)
+EXT_SIGNATURES = _ext_signatures()
+
+
 def load():
     """Load liboi.so (once).  Raises OiError when it has not been built."""
     global _lib
@@ -105,7 +118,7 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise OiError(f"{LIB_PATH} not built: run `make -C {_HERE}` (or __graft_entry__.build())")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in SIGNATURES.items():
+        for name, (restype, argtypes) in {**SIGNATURES, **EXT_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -244,7 +257,7 @@ def gpr_batch_device(xyt_dev, z_dev, offs, xs, mean, **kw):
 
 
 def _dense_args(xyt, z, offs, hyp, device_inputs, opt_kw, xs=None, toffs=None):
-    """What gpr_predict_multi, gpr_loo, gpr_lgo and gpr_sample share, checked:
+    """What gpr_predict_multi, gpr_loo, gpr_lgo, gpr_sample and gpr_predict_grad share, checked:
     the ragged batch (and, with ``toffs``, its targets ``xs`` [T x 3]), ``hyp``
     [ncell x 5], the observations' pointers, torch's current stream for device
     inputs, the options and a zeroed status.  Returns them as one namespace;
@@ -404,6 +417,47 @@ def gpr_sample(xyt, z, offs, xs, toffs, mean, hyp, nsamp, noise=False, jitter=0.
 def gpr_sample_device(xyt_dev, z_dev, offs, xs, toffs, mean, hyp, nsamp, **kw):
     """gpr_sample(..., device_inputs=True)."""
     return gpr_sample(xyt_dev, z_dev, offs, xs, toffs, mean, hyp, nsamp, device_inputs=True, **kw)
+
+
+def gpr_predict_grad(xyt, z, offs, xs, toffs, mean, hyp, blk=False, cov=False, device_inputs=False, **opt_kw):
+    """oi_gpr_predict_grad (include/oi_ext.h): the posterior of the field and of
+    its gradient at every cell's own targets (``xs`` [T x 3], cell c owning rows
+    toffs[c]:toffs[c+1]) at LINEAR hypers ``hyp`` [ncell x 5].  Returns (grad
+    [T x 3], gsd [T x 3], fs [T], sd [T], blk [T x 4 x 4] | None, cov | None,
+    status [ncell]): ``grad`` is the posterior mean of (df/dx, df/dy, df/dt) in
+    the inputs' units and ``gsd`` its standard deviation; ``fs`` / ``sd`` are
+    ``gpr_predict_multi``'s bit for bit; ``blk[t]`` is the 4 x 4 posterior
+    covariance of (f, df/dx, df/dy, df/dt) at target t; ``cov`` is the flat
+    array of the cells' (4 nt) x (4 nt) joint covariances back to back, index
+    4 t + k (``split_jcov`` cuts it up).  A cell whose factorisation fails has
+    status 1 and NaN results.  With device_inputs=True ``xyt`` / ``z`` are fp64
+    contiguous torch tensors on cuda:``device`` and the call runs on torch's
+    current stream; targets, offsets and hypers stay on the host."""
+    a = _dense_args(xyt, z, offs, hyp, device_inputs, opt_kw, xs, toffs)
+    T = int(a.toffs[-1])
+    grad = np.empty((T, 3))
+    gsd = np.empty((T, 3))
+    fs = np.empty(T)
+    sd = np.empty(T)
+    blka = np.empty((T, 4, 4)) if blk else None
+    nt = np.diff(a.toffs)
+    cova = np.empty(int((16 * nt * nt).sum())) if cov else None
+    _check(load().oi_gpr_predict_grad(*a.head, _ptr(a.xs), _ptr(a.toffs, ctypes.c_int64), float(mean), _ptr(a.hyp),
+                                      _ptr(grad), _ptr(gsd), _ptr(fs), _ptr(sd), _ptr(blka), _ptr(cova),
+                                      _ptr(a.status, ctypes.c_int32), ctypes.byref(a.opts)))
+    return grad, gsd, fs, sd, blka, cova, a.status
+
+
+def gpr_predict_grad_device(xyt_dev, z_dev, offs, xs, toffs, mean, hyp, **kw):
+    """gpr_predict_grad(..., device_inputs=True)."""
+    return gpr_predict_grad(xyt_dev, z_dev, offs, xs, toffs, mean, hyp, device_inputs=True, **kw)
+
+
+def split_jcov(cov, toffs):
+    """The flat ``cov`` of gpr_predict_grad as a list of 4 nt x 4 nt arrays (views)."""
+    m = 4 * np.diff(np.asarray(toffs, dtype=np.int64))
+    o = np.concatenate([[0], np.cumsum(m * m)])
+    return [cov[o[c]:o[c + 1]].reshape(m[c], m[c]) for c in range(len(m))]
 
 
 def split_cov(cov, toffs):

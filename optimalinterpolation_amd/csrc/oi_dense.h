@@ -1,9 +1,10 @@
 // What the dense-GP entry points share on the host (oi_predict.hip: many
 // targets per cell; oi_cv.hip: leave-one-out and leave-group-out; oi_sample.hip:
-// posterior draws): the per-cell descriptor, the workspace layout of a chunk
-// and of a cell, the argument checks, and Front, which runs a chunk up to the
-// solved X.  Host declarations only; the kernels that read a PCell and Front's
-// methods are in oi_predict.hip.
+// posterior draws; oi_grad.hip: the posterior of the field's gradient): the
+// per-cell descriptor, the workspace layout of a chunk and of a cell, the
+// argument checks, and Front, which runs a chunk up to the solved X.  Host
+// declarations only; the kernels that read a PCell and Front's methods are in
+// oi_predict.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -26,7 +27,7 @@ struct PCell {
   double* sc;        // n x 3 scaled inputs
   double* xsc;       // nt x 3 scaled targets
   double* K;         // Np x Np: K + sn2 I, then its Cholesky factor (lower)
-  double* X;         // (nt + 1) x n, leading dimension nt + 1
+  double* X;         // (rpt nt + 1) x n, leading dimension rpt nt + 1 (rpt rows per target: 1, the gradient's 4)
   double* cov;       // nt x nt (leading dimension nt) or null
   double* fs;        // nt
   double* sd;        // nt
@@ -63,26 +64,34 @@ struct DenseChunk {
 DenseChunk dense_chunk(Carver& cv, const DenseIn& in, int64_t n0, int64_t nn, const double* xs, int64_t tt,
                        int64_t no, int64_t nc, int64_t cc);
 // One cell's own: scaled inputs 3 n and targets 3 nt, K Np^2, the factor's
-// diagonal-block inverses 64 Np, X (nt + 1) n; leave-one-out adds their
+// diagonal-block inverses 64 Np, X (rpt nt + 1) n; leave-one-out adds their
 // transposes 64 Np and the lpl partials Np / 64 (the sweep writes the panels of
 // W' into K above the diagonal blocks and needs no n x n array of its own).
 struct DenseCell {
   double *sc, *xsc, *K, *dinv, *wdt, *X, *part;
 };
-DenseCell dense_cell(Carver& cv, int64_t n, int64_t nt, bool loo);
-int64_t dense_cell_doubles(int64_t n, int64_t nt, bool cov, bool host_inputs, bool loo);
+DenseCell dense_cell(Carver& cv, int64_t n, int64_t nt, bool loo, int64_t rpt = 1);
+// with cov the chunk-wide share holds the cell's (rpt nt)^2
+int64_t dense_cell_doubles(int64_t n, int64_t nt, bool cov, bool host_inputs, bool loo, int64_t rpt = 1);
 
 // The checks every entry makes after its offsets, in their order: null status,
 // null hyp, null xyt / z with observations, then `missing` (the entry's own
 // null-pointer message, or null), then every cell's arrays against oila's
-// 32-bit byte offsets: K always, and what `lim` names of X (nt + 1) n, cov
-// nt^2, the padded C Ntp^2 and nt nsamp.  toffs may be null (no targets).
+// 32-bit byte offsets: K always, and what `lim` names of X (rpt nt + 1) n (and
+// its row count rpt nt + 1 alone, which a cell without observations must keep
+// an int as well), cov
+// (rpt nt)^2, the padded C Ntp^2 and nt nsamp.  toffs may be null (no targets).
 struct DenseLimits {
   bool X, cov, C;
-  int64_t nsamp;  // < 0: no samples
+  int64_t nsamp;    // < 0: no samples
+  int64_t rpt = 1;  // rows of X (and of cov) per target
 };
 int dense_check(const double* xyt, const double* z, const int64_t* offs, const int64_t* toffs, int64_t ncell,
                 const double* hyp, const int32_t* status, const char* missing, const DenseLimits& lim);
+
+// An entry's own generator of X: launches on st over the chunk's nc cells (dc),
+// none of which has more than nmax observations or ntmax targets
+using XGen = void (*)(const PCell* dc, int64_t nmax, int64_t ntmax, unsigned nc, hipStream_t st);
 
 // What the entries share per chunk: the workspace, staging, carving, the PCell
 // descriptors, generation, Cholesky and solve; status copy and hand-over.
@@ -93,6 +102,8 @@ struct Front {
   const double* hyp;
   const double mean;
   const bool loo;
+  const int64_t rpt;  // rows of X per target
+  const XGen xgen;    // the caller's X generator, or null: k_pm_xgen
   hipStream_t st = in.st;
   oila::Stager la;
   StageTimer sg;
@@ -108,7 +119,7 @@ struct Front {
   double fl_chol, fl_solve, by_gen;
 
   Front(const oi_options& o, const double* xyt, const double* z, const int64_t* offs, const double* hyp, double mean,
-        bool loo, const char* const* stages, int count);
+        bool loo, const char* const* stages, int count, int64_t rpt = 1, XGen xgen = nullptr);
   // the chunks' cuts (plan_chunks) and the workspace that holds the largest
   template <class F>
   std::vector<int64_t> plan(int64_t ncell, int64_t slack, const char* what, F&& cell_doubles) {

@@ -31,8 +31,9 @@
 // cell's results do not depend on its batch mates or on the chunking.
 //
 // Front, the part of a chunk up to the solved X, and the layout and checks of
-// oi_dense.h are defined here too: oi_cv.hip (leave-one-out, leave-group-out)
-// and oi_sample.hip (posterior draws) run on them.
+// oi_dense.h are defined here too: oi_cv.hip (leave-one-out, leave-group-out),
+// oi_sample.hip (posterior draws) and oi_grad.hip (the gradient's posterior,
+// four rows of X per target from its own generator) run on them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -226,7 +227,7 @@ DenseChunk dense_chunk(Carver& cv, const DenseIn& in, int64_t n0, int64_t nn, co
   k.cov = cc >= 0 ? cv.take(cc) : nullptr;
   return k;
 }
-DenseCell dense_cell(Carver& cv, int64_t n, int64_t nt, bool loo) {
+DenseCell dense_cell(Carver& cv, int64_t n, int64_t nt, bool loo, int64_t rpt) {
   const int64_t Np = up(n, 64);
   DenseCell a;
   a.sc = cv.take(3 * n);
@@ -234,15 +235,15 @@ DenseCell dense_cell(Carver& cv, int64_t n, int64_t nt, bool loo) {
   a.K = cv.take(Np * Np);
   a.dinv = cv.take(Np * 64);
   a.wdt = loo ? cv.take(Np * 64) : nullptr;
-  a.X = cv.take((nt + 1) * n);
+  a.X = cv.take((rpt * nt + 1) * n);
   a.part = loo ? cv.take(Np / 64) : nullptr;
   return a;
 }
-int64_t dense_cell_doubles(int64_t n, int64_t nt, bool cov, bool host_inputs, bool loo) {
+int64_t dense_cell_doubles(int64_t n, int64_t nt, bool cov, bool host_inputs, bool loo, int64_t rpt) {
   Carver own, share{nullptr, 0, 1};
-  dense_cell(own, n, nt, loo);
+  dense_cell(own, n, nt, loo, rpt);
   dense_chunk(share, DenseIn{nullptr, nullptr, host_inputs, nullptr}, 0, n, nullptr, nt, loo ? n : nt, 1,
-              cov ? nt * nt : -1);
+              cov ? (rpt * nt) * (rpt * nt) : -1);
   return own.off + share.off;
 }
 
@@ -256,7 +257,9 @@ int dense_check(const double* xyt, const double* z, const int64_t* offs, const i
   for (int64_t c = 0; c < ncell; ++c) {
     const int64_t n = offs[c + 1] - offs[c], nt = toffs ? toffs[c + 1] - toffs[c] : 0, Np = up(n, 64),
                   Ntp = up(nt, 64);
-    if (Np * Np >= LIM || (lim.X && (nt + 1) * n >= LIM) || (lim.cov && nt * nt >= LIM) ||
+    const int64_t rows = lim.rpt * nt;
+    if (Np * Np >= LIM || (lim.X && (rows + 1 >= LIM || (rows + 1) * n >= LIM)) ||
+        (lim.cov && rows * rows >= LIM) ||
         (lim.C && Ntp * Ntp >= LIM) || (lim.nsamp > 0 && nt >= LIM / lim.nsamp)) {
       std::vector<const char*> names{"K"};
       if (lim.X) names.push_back("X");
@@ -273,9 +276,9 @@ int dense_check(const double* xyt, const double* z, const int64_t* offs, const i
 }
 
 Front::Front(const oi_options& o, const double* xyt, const double* z, const int64_t* offs, const double* hyp,
-             double mean, bool loo, const char* const* stages, int count)
+             double mean, bool loo, const char* const* stages, int count, int64_t rpt, XGen xgen)
     : o(o), in{xyt, z, o.device_inputs == 0, (hipStream_t)o.stream}, offs(offs), hyp(hyp), mean(mean), loo(loo),
-      sg(stages, count) {
+      rpt(rpt), xgen(xgen), sg(stages, count) {
   la.bind(st);
   sg.on = o.profile != 0;
   sg.st = st;
@@ -295,20 +298,21 @@ void Front::begin(int64_t c0_, int64_t c1, const double* xs, int64_t tt, int64_t
 PCell& Front::add(int64_t c, int64_t nt, int64_t toff, DenseCell& a) {
   const int64_t r0 = offs[c] - offs[c0], n = offs[c + 1] - offs[c], q = c - c0;
   const double* h = hyp + c * 5;
-  a = dense_cell(cv, n, nt, loo);
+  const int rows = (int)(rpt * nt + 1);  // of X
+  a = dense_cell(cv, n, nt, loo, rpt);
   const PCell p{.x = k.x ? k.x + r0 * 3 : nullptr, .z = k.z ? k.z + r0 : nullptr, .xs = k.xs + toff * 3, .sc = a.sc,
                 .xsc = a.xsc, .K = a.K, .X = a.X, .fs = k.mu + toff, .sd = k.sd + toff, .lz = k.lz + q,
                 .info = k.flag + q, .status = k.flag + nc + q, .n = (int)n, .nt = (int)nt, .Np = (int)up(n, 64),
                 .l0 = h[0], .l1 = h[1], .l2 = h[2], .sf2 = h[3], .sn2 = h[4], .mean = mean};
   if (n > 0) {
     chol.push_back(oila::Chol{p.K, a.dinv, p.info, p.Np, p.Np});
-    trsm.push_back(oila::TrsmRLT{p.X, p.K, a.dinv, p.nt + 1, p.n, p.nt + 1, p.Np});
+    trsm.push_back(oila::TrsmRLT{p.X, p.K, a.dinv, rows, p.n, rows, p.Np});
   }
   nmax = std::max(nmax, n);
   ntmax = std::max(ntmax, nt);
   pts = std::max(pts, n + nt);
-  xel = std::max(xel, (nt + 1) * n);
-  const double dn = (double)n, dt = (double)nt;
+  xel = std::max(xel, (int64_t)rows * n);
+  const double dn = (double)n, dt = (double)(rows - 1);
   fl_chol += dn * dn * dn / 3.0;
   fl_solve += (dt + 1.0) * dn * dn;
   by_gen += 8.0 * (dn * dn / 2.0 + (dt + 1.0) * dn);
@@ -327,7 +331,11 @@ const PCell* Front::factor(const char* entry, int s_gen, int s_chol, int s_solve
   if (nmax > 0) {
     hipLaunchKernelGGL(k_pm_kgen, dim3(Tn, Tn, gz), dim3(256), 0, st, dc);
     KCHK();
-    hipLaunchKernelGGL(k_pm_xgen, dim3(blocks(xel, 256), gz), dim3(256), 0, st, dc);
+    if (xgen) {
+      xgen(dc, nmax, ntmax, gz, st);
+    } else {
+      hipLaunchKernelGGL(k_pm_xgen, dim3(blocks(xel, 256), gz), dim3(256), 0, st, dc);
+    }
     KCHK();
   }
   sg.end();

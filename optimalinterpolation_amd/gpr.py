@@ -219,6 +219,30 @@ def sample_cells(cells, xs, toffs, nsamp, opt=True, x0=None, hyp=None, **kw):
     return samples, fs, sd, out8, np.maximum(status, st)
 
 
+def grad_cells(cells, xs, toffs, opt=True, x0=None, hyp=None, **kw):
+    """The posterior of the field's gradient for every cell of a RaggedCells
+    object at its own list of targets (``oi_gpr_predict_grad``; ``xs`` [T x 3],
+    cell c owning rows toffs[c]:toffs[c+1]).
+
+    The fit is exactly ``loo_cells``': ``opt=True`` fits the hypers as
+    ``gpr_cells(opt=True)`` does and differentiates at the fitted hypers;
+    ``opt=False`` does so at ``hyp`` [ncell x 5].  ``blk`` and ``cov`` go to
+    ``_lib.gpr_predict_grad``; the other keywords are options.  Returns ``(grad
+    [T x 3], gsd [T x 3], fs [T], sd [T], blk [T x 4 x 4] | None, cov_list |
+    None, out8, status)``: ``grad`` / ``gsd`` are the posterior mean and
+    standard deviation of (df/dx, df/dy, df/dt) -- the slope in m/m and the
+    growth rate in m/day -- ``fs`` / ``sd`` are ``gpr_predict_multi``'s,
+    ``cov_list[c]`` the (4 nt_c) x (4 nt_c) joint covariance of cell c (index
+    4 t + k), ``out8`` what ``gpr_cells`` returns, and ``status[c]`` the maximum
+    of the fit's and the gradient's."""
+    want = {k: kw.pop(k) for k in ('blk', 'cov') if k in kw}
+    o, out8, status, h = _fit_then(cells, opt, x0, hyp, kw)
+    grad, gsd, fs, sd, blk, cv, st = _lib.gpr_predict_grad(cells.xyt, cells.z, cells.offs, xs, toffs, cells.mean, h,
+                                                           **want, **o)
+    return (grad, gsd, fs, sd, blk, (_lib.split_jcov(cv, toffs) if cv is not None else None), out8,
+            np.maximum(status, st))
+
+
 def site_groups(xyt, offs):
     """Labels [N] that join the bitwise-equal (x, y, t) rows of a cell -- the
     observations of several satellites binned to one site -- for

@@ -201,6 +201,26 @@ def GPR_sample(x, y, xs, ell, sf2, sn2, mean, nsamp, seed=0, noise=False):
     return mean + samples, mean + f0, sd
 
 
+def GPR_grad(x, y, xs, ell, sf2, sn2, mean):
+    """The posterior of one cell's full-GP field and of its gradient at the
+    targets ``xs`` [ns x 3] in NB1 GPR's argument style (``y`` the residual
+    outputs, ``mean`` added back): (grad [ns x 3], gsd [ns x 3], fs [ns],
+    sd [ns], blk [ns x 4 x 4]).  ``grad`` / ``gsd`` are the mean and standard
+    deviation of (df/dx, df/dy, df/dt), ``fs`` / ``sd`` are ``GPR``'s, and
+    ``blk[t]`` the joint covariance of (f, df/dx, df/dy, df/dt) at target t.
+    LinAlgError where the cell's Cholesky factorisation fails
+    (``oi_gpr_predict_grad``)."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1, 3)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    xs = np.asarray(xs, dtype=np.float64).reshape(-1, 3)
+    hyp = np.array([[ell[0], ell[1], ell[2], sf2, sn2]], dtype=np.float64)
+    grad, gsd, f0, sd, blk, _, status = _lib.gpr_predict_grad(x, y, [0, len(y)], xs, [0, len(xs)], 0.0, hyp,
+                                                              blk=True, **options)
+    if status[0] != 0:
+        raise np.linalg.LinAlgError("Cholesky factorisation failed")
+    return grad, gsd, mean + f0, sd, blk
+
+
 def GPR_lgo(x, y, group, ell, sf2, sn2, mean):
     """Leave-group-out cross-validation of one cell of the full GP in
     ``GPR_loo``'s style: (mu [n], sd [n], lpd [n], d2 [n], lpl).  ``group`` [n]
