@@ -36,23 +36,21 @@
 // tridiagonalisation and the tridiagonal eigenpairs, batched MFMA products for
 // the orthogonalisation and the back-transform.  A Runner evaluates a chunk
 // of cells phase by phase on one stream; independent Runners (the groups of a
-// fit) overlap on streams of their own.  Per-cell status comes back in one
-// copy at the end.
+// fit, oi_nystrom_fit.hip) overlap on streams of their own.  Per-cell status
+// comes back in one copy at the end.  The host declarations are in
+// oi_nystrom.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <memory>
 #include <cstdint>
-#include <deque>
-#include <string>
 #include <vector>
 
 #include "oi_gemm.h"
 #include "oi_host.h"
 #include "oi_linalg.h"
 #include "oi_matern.h"
+#include "oi_nystrom.h"
 
 #pragma clang fp contract(off)
 
@@ -425,37 +423,17 @@ __global__ void __launch_bounds__(256) k_nys_cov_mfma(const double* __restrict__
       }
 }
 
-// ------------------------------------------------------------------- host --
-
-// opts.profile: HIP events around each stage of each cell, summed per stage
-// into oi_profile_json (algorithmic flops / bytes per stage alongside)
-enum { S_BUILD, S_EIGH, S_EIGH_VEC, S_EIGH_ORTH, S_EIGH_BACK, S_PANEL, S_KI, S_APPLY, S_LOGDET, S_GRAD,
-       S_PRED, S_PREDM, S_COUNT };
-// nys_eigh = the Householder tridiagonalisation; the eigensolver's other phases
-// are timed as their own stages
-const char* kStage[S_COUNT] = {"nys_build",  "nys_eigh",   "nys_eigh_vectors", "nys_eigh_orth",
-                               "nys_eigh_back", "nys_panels", "nys_ki_gemm", "nys_apply",
-                               "nys_logdet", "nys_grad",   "nys_predict", "nys_predict_multi"};
-// per-cell device results: [r.A, sum log diag(L) + sum log st / 2, g0..g4 raw
-// sums, k*.A, |k*|^2, |W k*|^2]
-constexpr int NRES = 10;
-// per-cell infos: [eigh, potrf(B)] (LAPACK's info semantics)
-constexpr int NINFO = 2;
-
 }  // namespace
 
-namespace {
+// ------------------------------------------------------------------- host --
 
-// Validated ragged batch + the device-side state of one liboi call.
-struct Batch {
-  const double* xyt;
-  const double* y;
-  const int64_t* offs;
-  int64_t ncell;
-  const int64_t* sel;
-  const int64_t* soffs;
-  int64_t nmax = 0, mmax = 0;
-};
+namespace oi_nys {
+
+// nys_eigh = the Householder tridiagonalisation; the eigensolver's other phases
+// are timed as their own stages
+const char* const kStage[S_COUNT] = {"nys_build",  "nys_eigh",   "nys_eigh_vectors", "nys_eigh_orth",
+                                     "nys_eigh_back", "nys_panels", "nys_ki_gemm", "nys_apply",
+                                     "nys_logdet", "nys_grad",   "nys_predict", "nys_predict_multi"};
 
 int check_batch(Batch& b) {
   if (b.ncell < 0) return oi_set_last_error(OI_E_ARG, "negative ncell");
@@ -483,699 +461,415 @@ int check_hypers(const double* hyp, int64_t ncell) {
   return 0;
 }
 
-// One cell's inputs on the device: the row of the cell table a Runner reads.
-struct CellSrc {
-  const double* x;     // n x 3
-  const double* y;     // n (outputs minus the prior mean, as NB1 passes them)
-  const int64_t* sel;  // M inducing rows, 0-based within the cell
-  const double* xs;    // 3 (prediction target) or null
-  int64_t n, M;
-};
-
-// Outcome of one cell at one hyper point (host side).
-struct CellOut {
-  double nlz, grad[5], fs, sd, sprior;
-  int status;
-};
-
-// Device copy of one validated batch (inputs when they came from the host,
-// inducing rows, targets) and its rows of the cell table.
-// Allocated and filled on stream `st` (stream-ordered; the constructor
-// returns once the copies are done) and freed on it: a session orders `st`
-// after every group's last use before dropping a batch.
-struct BatchDev {
-  DevBuf hx, hy, dsel, dxs;
-  std::vector<CellSrc> rows;
-  BatchDev(const Batch& b, const double* xs, bool device_inputs, hipStream_t st) {
-    const int64_t N = b.offs[b.ncell], S = b.soffs[b.ncell];
-    const double* dx = b.xyt;
-    const double* dy = b.y;
-    if (!device_inputs) {
-      hx.alloc_async(N * 3 * 8, st);
-      hy.alloc_async(N * 8, st);
-      HC(hipMemcpyAsync(hx.p, b.xyt, N * 3 * 8, hipMemcpyHostToDevice, st));
-      HC(hipMemcpyAsync(hy.p, b.y, N * 8, hipMemcpyHostToDevice, st));
-      dx = hx.as<double>();
-      dy = hy.as<double>();
-    }
-    dsel.alloc_async(S * 8, st);
-    HC(hipMemcpyAsync(dsel.p, b.sel, S * 8, hipMemcpyHostToDevice, st));
-    if (xs) {
-      dxs.alloc_async(b.ncell * 3 * 8, st);
-      HC(hipMemcpyAsync(dxs.p, xs, b.ncell * 3 * 8, hipMemcpyHostToDevice, st));
-    }
-    HC(hipStreamSynchronize(st));  // host arrays may go away once submit returns
-    rows.resize(b.ncell);
-    for (int64_t c = 0; c < b.ncell; ++c)
-      rows[c] = CellSrc{dx + b.offs[c] * 3, dy + b.offs[c], dsel.as<int64_t>() + b.soffs[c],
-                        xs ? dxs.as<double>() + c * 3 : nullptr, b.offs[c + 1] - b.offs[c],
-                        b.soffs[c + 1] - b.soffs[c]};
+BatchDev::BatchDev(const Batch& b, const double* xs, bool device_inputs, hipStream_t st) {
+  const int64_t N = b.offs[b.ncell], S = b.soffs[b.ncell];
+  const double* dx = b.xyt;
+  const double* dy = b.y;
+  if (!device_inputs) {
+    hx.alloc_async(N * 3 * 8, st);
+    hy.alloc_async(N * 8, st);
+    HC(hipMemcpyAsync(hx.p, b.xyt, N * 3 * 8, hipMemcpyHostToDevice, st));
+    HC(hipMemcpyAsync(hy.p, b.y, N * 8, hipMemcpyHostToDevice, st));
+    dx = hx.as<double>();
+    dy = hy.as<double>();
   }
-};
+  dsel.alloc_async(S * 8, st);
+  HC(hipMemcpyAsync(dsel.p, b.sel, S * 8, hipMemcpyHostToDevice, st));
+  if (xs) {
+    dxs.alloc_async(b.ncell * 3 * 8, st);
+    HC(hipMemcpyAsync(dxs.p, xs, b.ncell * 3 * 8, hipMemcpyHostToDevice, st));
+  }
+  HC(hipStreamSynchronize(st));  // host arrays may go away once submit returns
+  rows.resize(b.ncell);
+  for (int64_t c = 0; c < b.ncell; ++c)
+    rows[c] = CellSrc{dx + b.offs[c] * 3, dy + b.offs[c], dsel.as<int64_t>() + b.soffs[c],
+                      xs ? dxs.as<double>() + c * 3 : nullptr, b.offs[c + 1] - b.offs[c],
+                      b.soffs[c + 1] - b.soffs[c]};
+}
 
-// Many-target prediction of one call (oi_nystrom_predict_multi): the targets
-// and outputs of every cell on the device, and the scratch of one cell (sized
-// for the call's largest, reused from cell to cell in stream order).
-struct MultiDev {
-  const double* xs = nullptr;      // [T x 3] targets (device)
-  const int64_t* toffs = nullptr;  // [ncell + 1] (host): cell c owns rows toffs[c] .. toffs[c+1]-1
-  const int64_t* coffs = nullptr;  // [ncell + 1] (host): cell c's covariance starts at coffs[c]
-  double* fs = nullptr;            // [T]
-  double* var = nullptr;           // [T] diag(Kxs - err)
-  double* cov = nullptr;           // [coffs[ncell]] or null
-  double *ts = nullptr, *KxT = nullptr, *VT = nullptr, *Kp = nullptr, *Vp = nullptr;
+Runner::Runner(const std::vector<CellSrc>* tab, int64_t nmax, int64_t mmax, int64_t cap, const oi_options& o, bool obj,
+               bool pred, bool own_stream)
+    : tab_(tab), cap_(cap), st_((hipStream_t)o.stream), obj_(obj), pred_(pred) {
+  if (own_stream) {
+    own_.create();
+    st_ = own_.s;
+  }
+  hres_.reserve(cap * NRES * 8);
+  hinfo_.reserve(cap * NINFO * sizeof(int32_t));
+  hr_ = hres_.as<double>();
+  hi_ = hinfo_.as<int32_t>();
+  la_.bind(st_);
+  sg_.on = o.profile != 0;
+  sg_.st = st_;
+  const int64_t fd = Fixed::doubles(nmax, mmax, cap, obj, pred, kn_.fused);
+  fixed_.alloc((size_t)fd * 8);
+  Carver cf{fixed_.as<double>()};
+  fx_.layout(cf, nmax, mmax, cap, obj, pred, kn_.fused);
+  if (cf.off > fd) throw HipErr{"Runner: fixed workspace layout exceeds its estimate"};
+  // the slot arrays: chunk <= 64 cells and <= 1/4 of the HBM that is free now
+  // that the fixed part exists
+  const int64_t Mpmax = Mp(mmax);
+  const size_t per = (size_t)Slots::doubles(1, nmax, Mpmax, 1) * 8;
+  size_t fr = 0, tot = 0;
+  HC(hipMemGetInfo(&fr, &tot));
+  chunk_ = std::min<int64_t>(std::min<int64_t>(64, cap), std::max<int64_t>(1, (int64_t)(fr / 4 / per)));
+  const int64_t sd = Slots::doubles(chunk_, nmax, Mpmax);
+  slots_.alloc((size_t)sd * 8);
+  Carver cs{slots_.as<double>()};
+  sl_.layout(cs, chunk_, nmax, Mpmax);
+  if (cs.off > sd) throw HipErr{"Runner: slot workspace layout exceeds its estimate"};
+}
+Runner::~Runner() {  // the members (buffers first, the stream last) go after the stream's work
+  if (own_.s) (void)hipStreamSynchronize(own_.s);
+}
 
-  // One cell's scratch in doubles, array by array: scaled targets, Kxsx'
-  // (nt x n), V' (nt x M) and their zero-padded k-major tiles.
-  struct Scratch {
-    int64_t ts = 0, KxT = 0, VT = 0, Kp = 0, Vp = 0;
-    void grow(int64_t n, int64_t M, int64_t nt) {
-      const int64_t Tt = (nt + 63) / 64;
-      ts = std::max(ts, 3 * nt), KxT = std::max(KxT, nt * n), VT = std::max(VT, nt * M);
-      Kp = std::max(Kp, (n + 63) / 64 * Tt * 4096), Vp = std::max(Vp, (M + 63) / 64 * Tt * 4096);
-    }
-  };
-  // The workspace, described once: the call's T targets and outputs (covd
-  // covariance elements, none if negative), then one cell's scratch.  On a
-  // counting Carver: the size of the call, or (T = 0) of one cell's scratch.
-  void layout(Carver& cv, int64_t T, int64_t covd, const Scratch& s, const double* xs_host, hipStream_t st) {
-    xs = stage_host(cv, xs_host, 3 * T, st);
-    fs = cv.take(T);
-    var = cv.take(T);
-    cov = covd >= 0 ? cv.take(covd) : nullptr;
-    ts = cv.take(s.ts);
-    KxT = cv.take(s.KxT);
-    VT = cv.take(s.VT);
-    Kp = cv.take(s.Kp);
-    Vp = cv.take(s.Vp);
-  }
-  static int64_t doubles(int64_t T, int64_t covd, const Scratch& s) {
-    Carver cv;
-    MultiDev().layout(cv, T, covd, s, nullptr, nullptr);
-    return cv.off;
-  }
-};
+void Runner::run(const std::vector<int64_t>& cells, const double* hyp, double mean, CellOut* out) {
+  mean_ = mean;
+  enqueue(cells, hyp);
+  collect(out);
+}
+void Runner::run_all(int64_t ncell, const double* hyp, double mean, CellOut* out) {
+  std::vector<int64_t> cells(ncell);
+  for (int64_t c = 0; c < ncell; ++c) cells[c] = c;
+  run(cells, hyp, mean, out);
+}
 
-// The path's environment knobs, read once: by each Runner when it is built, by
-// the one-shot fit per call and by a session when it is created.
-struct Knobs {
-  // objective pass: fused MFMA kernel (default) or, with OI_NYS_FUSED=0, the
-  // n x n product forming Ki (oila::gemm) followed by k_nys_grad
-  bool fused = true;
-  // padding quantum (OI_NYS_PAD, default 32; 0 = no padding): K_mm and B of a
-  // cell are factored as diag(A, d I) of size Mp = M rounded up (the slot
-  // strides of the chunk arrays; results equal the unpadded path to rounding)
-  int padq = 32;
-  // the fit's groups of cells (OI_NYS_GROUPS), each with a stream and Runner of its own
-  int groups = 2;
-  // resident fitting cells per group of a session (OI_NYS_CAP): the batched
-  // eigensolver's per-column launches cost the same for 32 or 64 matrices, so a
-  // bigger chunk amortises them -- 5.46 / 6.69 / 6.63 cells/s at 32 / 64 / 128
-  // (--workload nystrom, one box, profiles/r05/nystrom_cap/)
-  int64_t cap = 64;
-  Knobs() {
-    if (const char* e = getenv("OI_NYS_FUSED")) fused = atoi(e) != 0;
-    if (const char* e = getenv("OI_NYS_PAD")) padq = std::max(0, atoi(e));
-    if (const char* e = getenv("OI_NYS_GROUPS")) groups = std::max(1, atoi(e));
-    if (const char* e = getenv("OI_NYS_CAP")) cap = std::max(1, atoi(e));
+void Runner::enqueue(const std::vector<int64_t>& cells, const double* hyp) {
+  const int64_t nc = (int64_t)cells.size();
+  ncq_ = nc;
+  if (!nc) return;
+  if (nc > cap_) throw HipErr{"Runner: more cells than its capacity"};
+  cellv_ = cells;
+  hypv_.assign(hyp, hyp + nc * 5);
+  // positions sorted by M (equal-M cells adjacent for the batched factorisations)
+  order_.resize(nc);
+  for (int64_t k = 0; k < nc; ++k) order_[k] = k;
+  std::stable_sort(order_.begin(), order_.end(), [&](int64_t a, int64_t c) {
+    return Mof(cells[a]) < Mof(cells[c]);
+  });
+  HC(hipMemsetAsync(fx_.res, 0, nc * NRES * 8, st_));
+  HC(hipMemsetAsync(fx_.info, 0, nc * NINFO * sizeof(int32_t), st_));
+  for (int64_t p0 = 0; p0 < nc; p0 += chunk_) {
+    const int64_t p1 = std::min(nc, p0 + chunk_);
+    for (int64_t p = p0; p < p1; ++p) phase1(p, p - p0);
+    batched(p0, p1, 0);
+    batched3(p0, p1);
+    batched(p0, p1, 1);
+    for (int64_t p = p0; p < p1; ++p) phase5(p, p - p0);
   }
-};
-inline int64_t padded(int64_t M, int padq) { return padq > 0 ? up(M, padq) : M; }
+  HC(hipMemcpyAsync(hr_, fx_.res, nc * NRES * 8, hipMemcpyDeviceToHost, st_));
+  HC(hipMemcpyAsync(hi_, fx_.info, nc * NINFO * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+}
 
-// A Runner's device memory is two workspaces, each described once by a layout
-// function (on a counting Carver: its size).
-//
-// Fixed: what one Runner owns for its lifetime -- the results and infos of an
-// evaluation's cells (at most cap) and phase 5's per-cell scratch, reused from
-// cell to cell in stream order.
-struct Fixed {
-  double* res;           // [cap x NRES]
-  int32_t* info;         // [cap x NINFO]
-  double *Av, *tv;       // A (n), W r (M)
-  double *Wp, *Ki;       // objective: W' packed (fused) or Ki (n x n), the other null
-  double* part;          // objective: the tiles' partial sums
-  double *ks, *kv, *xsc; // predict: k*, W k*, the scaled target
-  void layout(Carver& cv, int64_t nmax, int64_t mmax, int64_t cap, bool obj, bool pred, bool fused) {
-    const int64_t nt = blocks(nmax, 64);
-    res = cv.take(cap * NRES);
-    info = reinterpret_cast<int32_t*>(cv.take((cap * NINFO + 1) / 2));
-    Av = cv.take(nmax);
-    tv = cv.take(mmax);
-    Wp = obj && fused ? cv.take(blocks(mmax, 64) * nt * 4096) : nullptr;
-    Ki = obj && !fused ? cv.take(nmax * nmax) : nullptr;
-    part = obj ? cv.take(5 * nt * nt) : nullptr;
-    ks = pred ? cv.take(nmax) : nullptr;
-    kv = pred ? cv.take(mmax) : nullptr;
-    xsc = pred ? cv.take(3) : nullptr;
-  }
-  static int64_t doubles(int64_t nmax, int64_t mmax, int64_t cap, bool obj, bool pred, bool fused) {
-    Carver cv;
-    Fixed().layout(cv, nmax, mmax, cap, obj, pred, fused);
-    return cv.off;
-  }
-};
-
-// Slots: the per-slot state of a chunk of ch cells (scaled inputs, K_mm -> u,
-// s, st, C -> W', B -> L, the eigensolver's workspace, the Cholesky's
-// diagonal-block inverses, K_nm, U1 -> ut), each array ch slots of one stride;
-// Mp is the padded mmax.
-struct Slots {
-  struct Arr {
-    double* p = nullptr;
-    int64_t stride = 0;
-    double* slot(int64_t q) const { return p + q * stride; }
-  };
-  Arr sc, sq, Kmm, eval, stl, C, B, EW, Dinv, Knm, U1;
-  void layout(Carver& cv, int64_t ch, int64_t nmax, int64_t Mp) {
-    auto arr = [&](int64_t stride) { return Arr{cv.take(ch * stride), stride}; };
-    sc = arr(3 * nmax);
-    sq = arr(3 * nmax);
-    Kmm = arr(Mp * Mp);
-    eval = arr(Mp);
-    stl = arr(Mp);
-    C = arr(nmax * Mp);
-    B = arr(Mp * Mp);
-    EW = arr((int64_t)oila::eigh_workspace_doubles((int)Mp));
-    Dinv = arr((Mp + 63) / 64 * 4096);
-    Knm = arr(nmax * Mp);
-    U1 = arr(nmax * Mp);
-  }
-  // quantum 1 with ch = 1: one slot's share, what sizes a chunk
-  static int64_t doubles(int64_t ch, int64_t nmax, int64_t Mp, int64_t quantum = 32) {
-    Carver cv{nullptr, 0, quantum};
-    Slots().layout(cv, ch, nmax, Mp);
-    return cv.off;
-  }
-};
-
-// Evaluates any subset of a validated batch's cells at given LINEAR hypers.
-//
-// The eigensolver runs one workgroup per matrix and the blocked Cholesky one
-// launch sequence for many matrices, so a run is phase-major over CHUNKS of
-// cells (sorted by M): (1) K_mm of every cell, (2) one batched eigh per
-// equal-padded-M group, (3) the n x M panels and B of every cell, (4) one
-// batched Cholesky per group, (5) the triangular solve, objective and
-// prediction of every cell.
-// Everything is launched on the Runner's one stream; what overlaps is the
-// Runners of different groups.  Per-slot state (scaled inputs, K_mm -> u, s,
-// st, K_nm, U1 -> ut, C, B -> L) lives in chunk-sized slot arrays; the
-// per-cell scratch of phase 5 is reused from cell to cell in stream order.
-class Runner {
- public:
-  // Reads cells from *tab (rows indexed by cell id; the table may grow between
-  // calls); every cell has n <= nmax, M <= mmax; at most `cap` cells per
-  // evaluation.  own_stream: work on a private stream (several Runners then
-  // overlap); otherwise on the caller's opts.stream
-  Runner(const std::vector<CellSrc>* tab, int64_t nmax, int64_t mmax, int64_t cap, const oi_options& o,
-         bool want_obj, bool want_pred, bool own_stream = false)
-      : tab_(tab), cap_(cap), st_((hipStream_t)o.stream), alloc_obj_(want_obj),
-        alloc_pred_(want_pred) {
-    if (own_stream) {
-      own_.create();
-      st_ = own_.s;
-    }
-    hres_.reserve(cap * NRES * 8);
-    hinfo_.reserve(cap * NINFO * sizeof(int32_t));
-    hr_ = hres_.as<double>();
-    hi_ = hinfo_.as<int32_t>();
-    la_.bind(st_);
-    sg_.on = o.profile != 0;
-    sg_.st = st_;
-    const int64_t fd = Fixed::doubles(nmax, mmax, cap, want_obj, want_pred, kn_.fused);
-    fixed_.alloc((size_t)fd * 8);
-    Carver cf{fixed_.as<double>()};
-    fx_.layout(cf, nmax, mmax, cap, want_obj, want_pred, kn_.fused);
-    if (cf.off > fd) throw HipErr{"Runner: fixed workspace layout exceeds its estimate"};
-    // the slot arrays: chunk <= 64 cells and <= 1/4 of the HBM that is free now
-    // that the fixed part exists
-    const int64_t Mpmax = Mp(mmax);
-    const size_t per = (size_t)Slots::doubles(1, nmax, Mpmax, 1) * 8;
-    size_t fr = 0, tot = 0;
-    HC(hipMemGetInfo(&fr, &tot));
-    chunk_ = std::min<int64_t>(std::min<int64_t>(64, cap), std::max<int64_t>(1, (int64_t)(fr / 4 / per)));
-    const int64_t sd = Slots::doubles(chunk_, nmax, Mpmax);
-    slots_.alloc((size_t)sd * 8);
-    Carver cs{slots_.as<double>()};
-    sl_.layout(cs, chunk_, nmax, Mpmax);
-    if (cs.off > sd) throw HipErr{"Runner: slot workspace layout exceeds its estimate"};
-  }
-  ~Runner() {  // the members (buffers first, the stream last) go after the stream's work
-    if (own_.s) (void)hipStreamSynchronize(own_.s);
-  }
-
-  // every later evaluation also predicts cell id c at its targets m->toffs[c] ..
-  // (fs, var, cov of *m, which must outlive those evaluations)
-  void set_multi(const MultiDev* m) { multi_ = m; }
-
-  // cells[k] at LINEAR hypers hyp[k*5 ..]; results into out[k]
-  void run(const std::vector<int64_t>& cells, const double* hyp, double mean, CellOut* out,
-           bool want_obj, bool want_pred) {
-    enqueue(cells, hyp, mean, want_obj, want_pred);
-    collect(out);
-  }
-  // the table's cells 0 .. ncell - 1
-  void run_all(int64_t ncell, const double* hyp, double mean, CellOut* out, bool want_obj, bool want_pred) {
-    std::vector<int64_t> cells(ncell);
-    for (int64_t c = 0; c < ncell; ++c) cells[c] = c;
-    run(cells, hyp, mean, out, want_obj, want_pred);
-  }
-
-  // queue one evaluation of cells[k] at hyp[k*5 ..] (copied) without waiting
-  void enqueue(const std::vector<int64_t>& cells, const double* hyp, double mean, bool want_obj,
-               bool want_pred) {
-    const int64_t nc = (int64_t)cells.size();
-    ncq_ = nc;
-    if (!nc) return;
-    if (nc > cap_) throw HipErr{"Runner: more cells than its capacity"};
-    if ((want_obj && !alloc_obj_) || (want_pred && !alloc_pred_))
-      throw HipErr{"Runner: stage not allocated"};
-    obj_ = want_obj;
-    pred_ = want_pred;
-    mean_ = mean;
-    cellv_ = cells;
-    hypv_.assign(hyp, hyp + nc * 5);
-    cells_ = &cellv_;
-    hyp_ = hypv_.data();
-    // positions sorted by M (equal-M cells adjacent for the batched factorisations)
-    order_.resize(nc);
-    for (int64_t k = 0; k < nc; ++k) order_[k] = k;
-    std::stable_sort(order_.begin(), order_.end(), [&](int64_t a, int64_t c) {
-      return Mof(cells[a]) < Mof(cells[c]);
-    });
-    HC(hipMemsetAsync(fx_.res, 0, nc * NRES * 8, st_));
-    HC(hipMemsetAsync(fx_.info, 0, nc * NINFO * sizeof(int32_t), st_));
-    for (int64_t p0 = 0; p0 < nc; p0 += chunk_) {
-      const int64_t p1 = std::min(nc, p0 + chunk_);
-      for (int64_t p = p0; p < p1; ++p) phase1(p, p - p0);
-      batched(p0, p1, 0);
-      batched3(p0, p1);
-      batched(p0, p1, 1);
-      for (int64_t p = p0; p < p1; ++p) phase5(p, p - p0);
-    }
-    HC(hipMemcpyAsync(hr_, fx_.res, nc * NRES * 8, hipMemcpyDeviceToHost, st_));
-    HC(hipMemcpyAsync(hi_, fx_.info, nc * NINFO * sizeof(int32_t), hipMemcpyDeviceToHost, st_));
-  }
-
-  // wait for the queued evaluation; out[k] for the enqueued cells[k]
-  void collect(CellOut* out) {
-    const int64_t nc = ncq_;
-    if (!nc) return;
-    const std::vector<int64_t>& cells = cellv_;
-    const double* hyp = hyp_;
-    const double mean = mean_;
-    HC(hipStreamSynchronize(st_));
-    sg_.flush();
-    la_.reset();  // every launch that read the staged descriptors has completed
-    const double inf = INFINITY, nan = NAN;
-    for (int64_t p = 0; p < nc; ++p) {
-      const int64_t k = order_[p], c = cells[k];
-      const int64_t n = (*tab_)[c].n, M = Mof(c);
-      const double sf2 = hyp[k * 5 + 3], sn2 = hyp[k * 5 + 4];
-      const double* rr = hr_ + p * NRES;
-      const int32_t* ii = hi_ + p * NINFO;
-      const bool bad = ii[0] != 0 || ii[1] != 0;  // NB1's LinAlgError (eigh / cholesky)
-      CellOut& r = out[k];
-      r.status = bad ? 1 : 0;
-      if (obj_) {
-        if (bad) {
-          r.nlz = inf;
-          for (int q = 0; q < 5; ++q) r.grad[q] = inf;
-        } else {
-          // det = slogdet(H)/2 = (M log sn2 + sum log st + 2 sum log diag L) / 2
-          const double det = (double)M * std::log(sn2) / 2.0 + rr[1];
-          r.nlz = (rr[0] / 2.0 + det) + (double)n * std::log(2.0 * M_PI) / 2.0;
-          r.grad[0] = rr[2] / 2.0;
-          r.grad[1] = rr[3] / 2.0;
-          r.grad[2] = rr[4] / 2.0;
-          r.grad[3] = rr[5] / 2.0;
-          r.grad[4] = sn2 * rr[6];
-        }
-      }
-      if (pred_) {
-        const double err = rr[8] / sn2 - rr[9];  // k*'Ki k* = |k*|^2/sn2 - |W k*|^2
-        r.fs = bad ? nan : mean + rr[7];
-        r.sd = bad ? nan : std::sqrt(sf2 - err);
-        r.sprior = std::sqrt(sf2);
-      }
-    }
-  }
-
- private:
-  int64_t Mof(int64_t c) const { return (*tab_)[c].M; }
-  int64_t Mp(int64_t M) const { return padded(M, kn_.padq); }
-
-  // which = 0: s, u = eigh(Kmm) (oila::eigh; u overwrites Kmm); 1: L = chol(B)
-  // (oila::cholesky, in place, with the diagonal-block inverses kept for the
-  // triangular solve) -- one batched call per run of slots with equal padded
-  // size, on the main stream
-  void batched(int64_t p0, int64_t p1, int which) {
-    for (int64_t g0 = p0; g0 < p1;) {
-      const int64_t M = Mp(Mof((*cells_)[order_[g0]]));  // padded size of the group
-      int64_t g1 = g0 + 1;
-      while (g1 < p1 && Mp(Mof((*cells_)[order_[g1]])) == M) ++g1;
-      const int iM = (int)M, cnt = (int)(g1 - g0);
-      const int64_t s0 = g0 - p0;
-      const double dM = (double)M;
-      if (which == 0) {
-        std::vector<oila::Eigh> es;
-        for (int q = 0; q < cnt; ++q)
-          es.push_back(oila::Eigh{sl_.Kmm.slot(s0 + q), sl_.eval.slot(s0 + q), sl_.EW.slot(s0 + q), iM, iM,
-                                  fx_.info + (g0 + q) * NINFO + 0});
-        // algorithmic flops per phase: tridiagonalisation 4/3 M^3, tridiagonal
-        // eigenpairs O(M^2), BCGS2 2 M^3, back-transform 2 M^3
-        const double m3 = dM * dM * dM * cnt;
-        const int kind[4] = {S_EIGH, S_EIGH_VEC, S_EIGH_ORTH, S_EIGH_BACK};
-        const double fl[4] = {4.0 / 3.0 * m3, 0.0, 2.0 * m3, 2.0 * m3};
-        oila::eigh(la_, st_, es, [&](int k) {
-          if (k > 0) sg_.end();
-          if (k < 4) sg_.begin(kind[k], fl[k], 0.0);
-        });
-      } else {
-        // L = chol(B); half log-determinants; then W' = C L^-T by a block
-        // triangular solve with the kept diagonal-block inverses
-        sg_.begin(S_PANEL, dM * dM * dM / 3 * cnt, 0.0);
-        std::vector<oila::Chol> cs;
-        for (int q = 0; q < cnt; ++q)
-          cs.push_back(oila::Chol{sl_.B.slot(s0 + q), sl_.Dinv.slot(s0 + q), fx_.info + (g0 + q) * NINFO + 1, iM, iM});
-        oila::cholesky(la_, st_, cs);
-        // the pad block is the identity: log 1 = 0 and st is 1 there (see batched3)
-        hipLaunchKernelGGL(k_nys_logdet, dim3(cnt), dim3(256), 0, st_, sl_.B.slot(s0), M, M, sl_.B.stride,
-                           sl_.stl.slot(s0), sl_.stl.stride, fx_.res + g0 * NRES, (int64_t)NRES);
-        KCHK();
-        // W' = C L^-T in place on each slot's C (n x M, leading dimension n): one
-        // batched right-looking block solve for the whole group
-        std::vector<oila::TrsmRLT> ts;
-        for (int q = 0; q < cnt; ++q) {
-          const CellRefs R = refs(g0 + q, s0 + q);
-          ts.push_back(oila::TrsmRLT{R.C, R.B, R.dinv, R.in, R.iM, R.in, R.iMp});
-        }
-        oila::trsm_right_lt(la_, st_, ts);
-        sg_.end();
-      }
-      g0 = g1;
-    }
-  }
-
-  struct CellRefs {
-    int64_t c, k, n, M, Mp;
-    int in, iM, iMp;
-    double dn, dM;
-    const double* x;
-    const double* r;
-    const int64_t* sl;
-    const double* hp;
-    double *sc, *sq, *Kmm, *s, *stl, *C, *B, *rs, *dinv;
-  };
-  CellRefs refs(int64_t p, int64_t slot) {
-    CellRefs R;
-    R.k = order_[p];
-    R.c = (*cells_)[R.k];
-    R.n = (*tab_)[R.c].n;
-    R.M = Mof(R.c);
-    R.Mp = Mp(R.M);
-    R.in = (int)R.n;
-    R.iM = (int)R.M;
-    R.iMp = (int)R.Mp;
-    R.dn = (double)R.n;
-    R.dM = (double)R.M;
-    R.x = (*tab_)[R.c].x;
-    R.r = (*tab_)[R.c].y;
-    R.sl = (*tab_)[R.c].sel;
-    R.hp = hyp_ + R.k * 5;
-    R.sc = sl_.sc.slot(slot);
-    R.sq = sl_.sq.slot(slot);
-    R.Kmm = sl_.Kmm.slot(slot);
-    R.s = sl_.eval.slot(slot);
-    R.stl = sl_.stl.slot(slot);
-    R.C = sl_.C.slot(slot);
-    R.B = sl_.B.slot(slot);
-    R.rs = fx_.res + p * NRES;
-    R.dinv = sl_.Dinv.slot(slot);
-    return R;
-  }
-
-  // phase 3 for a whole chunk: s clamp, st; Knm = SGPkernel(x, xs=x[sel]);
-  // U1 = Knm u; ut, C = Vi ut; B = diag(1/st) + ut' C -- the per-cell elementwise
-  // kernels, and each of the two n x M products as ONE batched oila::gemm over
-  // the chunk's cells (per-cell launches of ~1 000 64 x 64 tiles left the
-  // chip under-filled in the last wave of tiles)
-  void batched3(int64_t p0, int64_t p1) {
-    hipStream_t st = st_;
-    double fl = 0.0, by = 0.0;
-    for (int64_t p = p0; p < p1; ++p) {
-      const CellRefs R = refs(p, p - p0);
-      fl += 4 * R.dn * R.dM * R.dM;
-      by += 8.0 * R.dn * R.dM;
-    }
-    sg_.begin(S_PANEL, fl, by);
-    std::vector<oila::Gemm> g1, g2;
-    for (int64_t p = p0; p < p1; ++p) {
-      const CellRefs R = refs(p, p - p0);
-      double* Knm = sl_.Knm.slot(p - p0);
-      double* U1 = sl_.U1.slot(p - p0);
-      hipLaunchKernelGGL(k_nys_eigpost, dim3(blocks(R.Mp, 256)), dim3(256), 0, st, R.s, R.M, R.Mp,
-                         R.n, R.stl);
-      KCHK();
-      hipLaunchKernelGGL(k_nys_cross, dim3(blocks(R.n, 256), (unsigned)R.M), dim3(256), 0, st, R.sc,
-                         nullptr, R.n, R.sc, R.sl, R.hp[3], Knm, R.n);
-      KCHK();
-      g1.push_back(oila::Gemm{Knm, R.Kmm, U1, R.in, R.iM, R.iM, R.in, R.iMp, R.in, 1.0, 0.0, 0});  // U1 = Knm u
-      g2.push_back(oila::Gemm{U1, R.C, R.B, R.iM, R.iM, R.in, R.in, R.in, R.iMp, 1.0, 0.0, 0});    // B = ut' C
-    }
-    oila::gemm(la_, st, false, false, g1);
-    for (int64_t p = p0; p < p1; ++p) {  // ut (in place of U1) and C
-      const CellRefs R = refs(p, p - p0);
-      double* U1 = sl_.U1.slot(p - p0);
-      hipLaunchKernelGGL(k_nys_ut, dim3(blocks(R.n * R.M, 256)), dim3(256), 0, st, U1, R.n, R.M, R.s,
-                         std::sqrt(R.dM / R.dn), 1.0 / R.hp[4], U1, R.C);
-      KCHK();
-    }
-    oila::gemm(la_, st, true, false, g2);
-    for (int64_t p = p0; p < p1; ++p) {  // B += diag(1/st), pad block
-      const CellRefs R = refs(p, p - p0);
-      hipLaunchKernelGGL(k_nys_diag, dim3(blocks(R.M, 256)), dim3(256), 0, st, R.B, R.M, R.Mp, R.stl, 1,
-                         0.0);
-      KCHK();
-      if (R.Mp > R.M) {
-        hipLaunchKernelGGL(k_nys_pad, dim3(blocks(R.Mp, 256), (unsigned)R.Mp), dim3(256), 0, st, R.B,
-                           R.M, R.Mp, 1.0);
-        KCHK();
-      }
-    }
-    sg_.end();
-  }
-
-  // scaled inputs, Kmm (NB1 Nystroem: SGPkernel(x[sel]))
-  void phase1(int64_t p, int64_t slot) {
-    const CellRefs R = refs(p, slot);
-    hipStream_t st = st_;
-    sg_.begin(S_BUILD, 0.0, 8.0 * R.dM * R.dM);
-    hipLaunchKernelGGL(k_nys_scale, dim3(blocks(R.n, 256)), dim3(256), 0, st, R.x, R.n, R.hp[0],
-                       R.hp[1], R.hp[2], R.sc, obj_ ? R.sq : nullptr);
-    KCHK();
-    hipLaunchKernelGGL(k_nys_cross, dim3(blocks(R.M, 256), (unsigned)R.M), dim3(256), 0, st, R.sc,
-                       R.sl, R.M, R.sc, R.sl, R.hp[3], R.Kmm, R.Mp);
-    KCHK();
-    if (R.Mp > R.M) {
-      // pad eigenvalue above every eigenvalue of K_mm (<= trace = M sf2), so the
-      // M real eigenpairs stay first in syevd's ascending order
-      hipLaunchKernelGGL(k_nys_pad, dim3(blocks(R.Mp, 256), (unsigned)R.Mp), dim3(256), 0, st,
-                         R.Kmm, R.M, R.Mp, 2.0 * R.dM * R.hp[3] + 1.0);
-      KCHK();
-    }
-    sg_.end();
-  }
-
-  // W' = C L^-T;  A = r/sn2 - W'(W r);  objective (Ki, fused pass);  predict
-  void phase5(int64_t p, int64_t slot) {
-    const CellRefs R = refs(p, slot);
-    hipStream_t st = st_;
-    const double sf2 = R.hp[3], isn2 = 1.0 / R.hp[4];
-    const double dn = R.dn, dM = R.dM;
-    double* Wt = R.C;  // n x M: W' = C L^-T, formed in place by batched()
-    double* Av = fx_.Av;
-    double* tv = fx_.tv;
-    StageTimer& sg = sg_;
-    sg.begin(S_APPLY, 2.0 * dM * dM * dn + 4.0 * dn * dM, 16.0 * dn * dM);
-    hipLaunchKernelGGL(k_nys_vi, dim3(blocks(R.n, 256)), dim3(256), 0, st, R.r, R.n, isn2, Av);
-    KCHK();
-    oila::gemv(la_, st, true, {oila::Gemv{Wt, R.r, tv, R.in, R.iM, R.in, 1.0, 0.0}});     // tv = W r
-    oila::gemv(la_, st, false, {oila::Gemv{Wt, tv, Av, R.in, R.iM, R.in, -1.0, 1.0}});   // A -= W' tv
-    sg.end();
+void Runner::collect(CellOut* out) {
+  const int64_t nc = ncq_;
+  if (!nc) return;
+  HC(hipStreamSynchronize(st_));
+  sg_.flush();
+  la_.reset();  // every launch that read the staged descriptors has completed
+  const double inf = INFINITY, nan = NAN;
+  for (int64_t p = 0; p < nc; ++p) {
+    const int64_t k = order_[p], c = cellv_[k];
+    const int64_t n = (*tab_)[c].n, M = Mof(c);
+    const double sf2 = hypv_[k * 5 + 3], sn2 = hypv_[k * 5 + 4];
+    const double* rr = hr_ + p * NRES;
+    const int32_t* ii = hi_ + p * NINFO;
+    const bool bad = ii[0] != 0 || ii[1] != 0;  // NB1's LinAlgError (eigh / cholesky)
+    CellOut& r = out[k];
+    r.status = bad ? 1 : 0;
     if (obj_) {
-      double* Ki = fx_.Ki;
-      sg.begin(S_LOGDET, 2.0 * dn, 16.0 * dn);
-      hipLaunchKernelGGL(k_nys_dot, dim3(1), dim3(256), 0, st, R.r, Av, R.n, R.rs + 0);
-      KCHK();
-      sg.end();
-      if (kn_.fused) {
-        // (W'W) tiles on the MFMA core, reduced against K, dK in the same kernel
-        const int Tn = (int)blocks(R.n, 64), Tk = (int)blocks(R.M, 64);
-        const int ntri = Tn * (Tn + 1) / 2;
-        sg.begin(S_KI, dn * dn * dM, 8.0 * dn * dM);
-        hipLaunchKernelGGL(k_nys_pack, dim3((unsigned)(Tn * Tk)), dim3(256), 0, st, Wt, R.n, R.M,
-                           Tn, fx_.Wp);
-        KCHK();
-        sg.end();
-        sg.begin(S_GRAD, dn * dn * dM, 0.0);
-        hipLaunchKernelGGL(k_nys_grad_mfma, dim3((unsigned)ntri), dim3(256), 0, st, fx_.Wp, Tn, Tk, Av, R.sc,
-                           R.sq, R.n, sf2, isn2, fx_.part);
-        KCHK();
-        hipLaunchKernelGGL(k_nys_partsum, dim3(1), dim3(256), 0, st, fx_.part, (int64_t)ntri, R.rs + 2);
-        KCHK();
-        sg.end();
+      if (bad) {
+        r.nlz = inf;
+        for (int q = 0; q < 5; ++q) r.grad[q] = inf;
       } else {
-        // Ki = Vi - W'W (OI_NYS_FUSED=0 only: one full oila::gemm product; the
-        // sweep below reads the lower half)
-        sg.begin(S_KI, 2.0 * dn * dn * dM, 8.0 * dn * dn);
-        oila::gemm(la_, st, false, true, {oila::Gemm{Wt, Wt, Ki, R.in, R.in, R.iM, R.in, R.in, R.in, -1.0, 0.0, 0}});
-        hipLaunchKernelGGL(k_nys_diag, dim3(blocks(R.n, 256)), dim3(256), 0, st, Ki, R.n, R.n, nullptr,
-                           0, isn2);
-        KCHK();
-        sg.end();
-        // the lower triangle of Ki read once (~4 n^2 bytes); inputs and A cache-resident
-        sg.begin(S_GRAD, 0.0, 4.0 * dn * dn);
-        const unsigned nt = blocks(R.n, 64);
-        hipLaunchKernelGGL(k_nys_grad, dim3(nt, nt), dim3(256), 0, st, Ki, Av, R.sc, R.sq, R.n, sf2, fx_.part);
-        KCHK();
-        hipLaunchKernelGGL(k_nys_partsum, dim3(1), dim3(256), 0, st, fx_.part, (int64_t)nt * nt, R.rs + 2);
-        KCHK();
-        sg.end();
+        // det = slogdet(H)/2 = (M log sn2 + sum log st + 2 sum log diag L) / 2
+        const double det = (double)M * std::log(sn2) / 2.0 + rr[1];
+        r.nlz = (rr[0] / 2.0 + det) + (double)n * std::log(2.0 * M_PI) / 2.0;
+        r.grad[0] = rr[2] / 2.0;
+        r.grad[1] = rr[3] / 2.0;
+        r.grad[2] = rr[4] / 2.0;
+        r.grad[3] = rr[5] / 2.0;
+        r.grad[4] = sn2 * rr[6];
       }
     }
     if (pred_) {
-      // k* = SGPkernel(x, xs=xs); fs = mean + k*.A; k*'Ki k* = |k*|^2/sn2 - |W k*|^2
-      sg.begin(S_PRED, 2.0 * dn * dM, 8.0 * dn * dM);
-      double* ks = fx_.ks;
-      double* kv = fx_.kv;
-      hipLaunchKernelGGL(k_nys_scale, dim3(1), dim3(64), 0, st, (*tab_)[R.c].xs,
-                         (int64_t)1, R.hp[0], R.hp[1], R.hp[2], fx_.xsc, nullptr);
+      const double err = rr[8] / sn2 - rr[9];  // k*'Ki k* = |k*|^2/sn2 - |W k*|^2
+      r.fs = bad ? nan : mean_ + rr[7];
+      r.sd = bad ? nan : std::sqrt(sf2 - err);
+      r.sprior = std::sqrt(sf2);
+    }
+  }
+}
+
+// which = 0: s, u = eigh(Kmm) (oila::eigh; u overwrites Kmm); 1: L = chol(B)
+// (oila::cholesky, in place, with the diagonal-block inverses kept for the
+// triangular solve) -- one batched call per run of slots with equal padded
+// size, on the main stream
+void Runner::batched(int64_t p0, int64_t p1, int which) {
+  for (int64_t g0 = p0; g0 < p1;) {
+    const int64_t M = Mp(Mof(cellv_[order_[g0]]));  // padded size of the group
+    int64_t g1 = g0 + 1;
+    while (g1 < p1 && Mp(Mof(cellv_[order_[g1]])) == M) ++g1;
+    const int iM = (int)M, cnt = (int)(g1 - g0);
+    const int64_t s0 = g0 - p0;
+    const double dM = (double)M;
+    if (which == 0) {
+      std::vector<oila::Eigh> es;
+      for (int q = 0; q < cnt; ++q)
+        es.push_back(oila::Eigh{sl_.Kmm.slot(s0 + q), sl_.eval.slot(s0 + q), sl_.EW.slot(s0 + q), iM, iM,
+                                fx_.info + (g0 + q) * NINFO + 0});
+      // algorithmic flops per phase: tridiagonalisation 4/3 M^3, tridiagonal
+      // eigenpairs O(M^2), BCGS2 2 M^3, back-transform 2 M^3
+      const double m3 = dM * dM * dM * cnt;
+      const int kind[4] = {S_EIGH, S_EIGH_VEC, S_EIGH_ORTH, S_EIGH_BACK};
+      const double fl[4] = {4.0 / 3.0 * m3, 0.0, 2.0 * m3, 2.0 * m3};
+      oila::eigh(la_, st_, es, [&](int k) {
+        if (k > 0) sg_.end();
+        if (k < 4) sg_.begin(kind[k], fl[k], 0.0);
+      });
+    } else {
+      // L = chol(B); half log-determinants; then W' = C L^-T by a block
+      // triangular solve with the kept diagonal-block inverses
+      sg_.begin(S_PANEL, dM * dM * dM / 3 * cnt, 0.0);
+      std::vector<oila::Chol> cs;
+      for (int q = 0; q < cnt; ++q)
+        cs.push_back(oila::Chol{sl_.B.slot(s0 + q), sl_.Dinv.slot(s0 + q), fx_.info + (g0 + q) * NINFO + 1, iM, iM});
+      oila::cholesky(la_, st_, cs);
+      // the pad block is the identity: log 1 = 0 and st is 1 there (see batched3)
+      hipLaunchKernelGGL(k_nys_logdet, dim3(cnt), dim3(256), 0, st_, sl_.B.slot(s0), M, M, sl_.B.stride,
+                         sl_.stl.slot(s0), sl_.stl.stride, fx_.res + g0 * NRES, (int64_t)NRES);
       KCHK();
-      hipLaunchKernelGGL(k_nys_cross, dim3(blocks(R.n, 256), 1), dim3(256), 0, st, R.sc, nullptr,
-                         R.n, fx_.xsc, nullptr, sf2, ks, R.n);
+      // W' = C L^-T in place on each slot's C (n x M, leading dimension n): one
+      // batched right-looking block solve for the whole group
+      std::vector<oila::TrsmRLT> ts;
+      for (int q = 0; q < cnt; ++q) {
+        const CellRefs R = refs(g0 + q, s0 + q);
+        ts.push_back(oila::TrsmRLT{R.C, R.B, R.dinv, R.in, R.iM, R.in, R.iMp});
+      }
+      oila::trsm_right_lt(la_, st_, ts);
+      sg_.end();
+    }
+    g0 = g1;
+  }
+}
+
+Runner::CellRefs Runner::refs(int64_t p, int64_t slot) {
+  CellRefs R;
+  R.k = order_[p];
+  R.c = cellv_[R.k];
+  R.n = (*tab_)[R.c].n;
+  R.M = Mof(R.c);
+  R.Mp = Mp(R.M);
+  R.in = (int)R.n;
+  R.iM = (int)R.M;
+  R.iMp = (int)R.Mp;
+  R.dn = (double)R.n;
+  R.dM = (double)R.M;
+  R.x = (*tab_)[R.c].x;
+  R.r = (*tab_)[R.c].y;
+  R.sl = (*tab_)[R.c].sel;
+  R.hp = hypv_.data() + R.k * 5;
+  R.sc = sl_.sc.slot(slot);
+  R.sq = sl_.sq.slot(slot);
+  R.Kmm = sl_.Kmm.slot(slot);
+  R.s = sl_.eval.slot(slot);
+  R.stl = sl_.stl.slot(slot);
+  R.C = sl_.C.slot(slot);
+  R.B = sl_.B.slot(slot);
+  R.rs = fx_.res + p * NRES;
+  R.dinv = sl_.Dinv.slot(slot);
+  return R;
+}
+
+// phase 3 for a whole chunk: s clamp, st; Knm = SGPkernel(x, xs=x[sel]);
+// U1 = Knm u; ut, C = Vi ut; B = diag(1/st) + ut' C -- the per-cell elementwise
+// kernels, and each of the two n x M products as ONE batched oila::gemm over
+// the chunk's cells (per-cell launches of ~1 000 64 x 64 tiles left the
+// chip under-filled in the last wave of tiles)
+void Runner::batched3(int64_t p0, int64_t p1) {
+  hipStream_t st = st_;
+  double fl = 0.0, by = 0.0;
+  for (int64_t p = p0; p < p1; ++p) {
+    const CellRefs R = refs(p, p - p0);
+    fl += 4 * R.dn * R.dM * R.dM;
+    by += 8.0 * R.dn * R.dM;
+  }
+  sg_.begin(S_PANEL, fl, by);
+  std::vector<oila::Gemm> g1, g2;
+  for (int64_t p = p0; p < p1; ++p) {
+    const CellRefs R = refs(p, p - p0);
+    double* Knm = sl_.Knm.slot(p - p0);
+    double* U1 = sl_.U1.slot(p - p0);
+    hipLaunchKernelGGL(k_nys_eigpost, dim3(blocks(R.Mp, 256)), dim3(256), 0, st, R.s, R.M, R.Mp,
+                       R.n, R.stl);
+    KCHK();
+    hipLaunchKernelGGL(k_nys_cross, dim3(blocks(R.n, 256), (unsigned)R.M), dim3(256), 0, st, R.sc,
+                       nullptr, R.n, R.sc, R.sl, R.hp[3], Knm, R.n);
+    KCHK();
+    g1.push_back(oila::Gemm{Knm, R.Kmm, U1, R.in, R.iM, R.iM, R.in, R.iMp, R.in, 1.0, 0.0, 0});  // U1 = Knm u
+    g2.push_back(oila::Gemm{U1, R.C, R.B, R.iM, R.iM, R.in, R.in, R.in, R.iMp, 1.0, 0.0, 0});    // B = ut' C
+  }
+  oila::gemm(la_, st, false, false, g1);
+  for (int64_t p = p0; p < p1; ++p) {  // ut (in place of U1) and C
+    const CellRefs R = refs(p, p - p0);
+    double* U1 = sl_.U1.slot(p - p0);
+    hipLaunchKernelGGL(k_nys_ut, dim3(blocks(R.n * R.M, 256)), dim3(256), 0, st, U1, R.n, R.M, R.s,
+                       std::sqrt(R.dM / R.dn), 1.0 / R.hp[4], U1, R.C);
+    KCHK();
+  }
+  oila::gemm(la_, st, true, false, g2);
+  for (int64_t p = p0; p < p1; ++p) {  // B += diag(1/st), pad block
+    const CellRefs R = refs(p, p - p0);
+    hipLaunchKernelGGL(k_nys_diag, dim3(blocks(R.M, 256)), dim3(256), 0, st, R.B, R.M, R.Mp, R.stl, 1,
+                       0.0);
+    KCHK();
+    if (R.Mp > R.M) {
+      hipLaunchKernelGGL(k_nys_pad, dim3(blocks(R.Mp, 256), (unsigned)R.Mp), dim3(256), 0, st, R.B,
+                         R.M, R.Mp, 1.0);
       KCHK();
-      hipLaunchKernelGGL(k_nys_dot, dim3(1), dim3(256), 0, st, ks, Av, R.n, R.rs + 7);
+    }
+  }
+  sg_.end();
+}
+
+// scaled inputs, Kmm (NB1 Nystroem: SGPkernel(x[sel]))
+void Runner::phase1(int64_t p, int64_t slot) {
+  const CellRefs R = refs(p, slot);
+  hipStream_t st = st_;
+  sg_.begin(S_BUILD, 0.0, 8.0 * R.dM * R.dM);
+  hipLaunchKernelGGL(k_nys_scale, dim3(blocks(R.n, 256)), dim3(256), 0, st, R.x, R.n, R.hp[0],
+                     R.hp[1], R.hp[2], R.sc, obj_ ? R.sq : nullptr);
+  KCHK();
+  hipLaunchKernelGGL(k_nys_cross, dim3(blocks(R.M, 256), (unsigned)R.M), dim3(256), 0, st, R.sc,
+                     R.sl, R.M, R.sc, R.sl, R.hp[3], R.Kmm, R.Mp);
+  KCHK();
+  if (R.Mp > R.M) {
+    // pad eigenvalue above every eigenvalue of K_mm (<= trace = M sf2), so the
+    // M real eigenpairs stay first in syevd's ascending order
+    hipLaunchKernelGGL(k_nys_pad, dim3(blocks(R.Mp, 256), (unsigned)R.Mp), dim3(256), 0, st,
+                       R.Kmm, R.M, R.Mp, 2.0 * R.dM * R.hp[3] + 1.0);
+    KCHK();
+  }
+  sg_.end();
+}
+
+// W' = C L^-T;  A = r/sn2 - W'(W r);  objective (Ki, fused pass);  predict
+void Runner::phase5(int64_t p, int64_t slot) {
+  const CellRefs R = refs(p, slot);
+  hipStream_t st = st_;
+  const double sf2 = R.hp[3], isn2 = 1.0 / R.hp[4];
+  const double dn = R.dn, dM = R.dM;
+  double* Wt = R.C;  // n x M: W' = C L^-T, formed in place by batched()
+  double* Av = fx_.Av;
+  double* tv = fx_.tv;
+  StageTimer& sg = sg_;
+  sg.begin(S_APPLY, 2.0 * dM * dM * dn + 4.0 * dn * dM, 16.0 * dn * dM);
+  hipLaunchKernelGGL(k_nys_vi, dim3(blocks(R.n, 256)), dim3(256), 0, st, R.r, R.n, isn2, Av);
+  KCHK();
+  oila::gemv(la_, st, true, {oila::Gemv{Wt, R.r, tv, R.in, R.iM, R.in, 1.0, 0.0}});     // tv = W r
+  oila::gemv(la_, st, false, {oila::Gemv{Wt, tv, Av, R.in, R.iM, R.in, -1.0, 1.0}});   // A -= W' tv
+  sg.end();
+  if (obj_) {
+    double* Ki = fx_.Ki;
+    sg.begin(S_LOGDET, 2.0 * dn, 16.0 * dn);
+    hipLaunchKernelGGL(k_nys_dot, dim3(1), dim3(256), 0, st, R.r, Av, R.n, R.rs + 0);
+    KCHK();
+    sg.end();
+    if (kn_.fused) {
+      // (W'W) tiles on the MFMA core, reduced against K, dK in the same kernel
+      const int Tn = (int)blocks(R.n, 64), Tk = (int)blocks(R.M, 64);
+      const int ntri = Tn * (Tn + 1) / 2;
+      sg.begin(S_KI, dn * dn * dM, 8.0 * dn * dM);
+      hipLaunchKernelGGL(k_nys_pack, dim3((unsigned)(Tn * Tk)), dim3(256), 0, st, Wt, R.n, R.M,
+                         Tn, fx_.Wp);
       KCHK();
-      hipLaunchKernelGGL(k_nys_dot, dim3(1), dim3(256), 0, st, ks, ks, R.n, R.rs + 8);
+      sg.end();
+      sg.begin(S_GRAD, dn * dn * dM, 0.0);
+      hipLaunchKernelGGL(k_nys_grad_mfma, dim3((unsigned)ntri), dim3(256), 0, st, fx_.Wp, Tn, Tk, Av, R.sc,
+                         R.sq, R.n, sf2, isn2, fx_.part);
       KCHK();
-      oila::gemv(la_, st, true, {oila::Gemv{Wt, ks, kv, R.in, R.iM, R.in, 1.0, 0.0}});  // kv = W k*
-      hipLaunchKernelGGL(k_nys_dot, dim3(1), dim3(256), 0, st, kv, kv, R.M, R.rs + 9);
+      hipLaunchKernelGGL(k_nys_partsum, dim3(1), dim3(256), 0, st, fx_.part, (int64_t)ntri, R.rs + 2);
+      KCHK();
+      sg.end();
+    } else {
+      // Ki = Vi - W'W (OI_NYS_FUSED=0 only: one full oila::gemm product; the
+      // sweep below reads the lower half)
+      sg.begin(S_KI, 2.0 * dn * dn * dM, 8.0 * dn * dn);
+      oila::gemm(la_, st, false, true, {oila::Gemm{Wt, Wt, Ki, R.in, R.in, R.iM, R.in, R.in, R.in, -1.0, 0.0, 0}});
+      hipLaunchKernelGGL(k_nys_diag, dim3(blocks(R.n, 256)), dim3(256), 0, st, Ki, R.n, R.n, nullptr,
+                         0, isn2);
+      KCHK();
+      sg.end();
+      // the lower triangle of Ki read once (~4 n^2 bytes); inputs and A cache-resident
+      sg.begin(S_GRAD, 0.0, 4.0 * dn * dn);
+      const unsigned nt = blocks(R.n, 64);
+      hipLaunchKernelGGL(k_nys_grad, dim3(nt, nt), dim3(256), 0, st, Ki, Av, R.sc, R.sq, R.n, sf2, fx_.part);
+      KCHK();
+      hipLaunchKernelGGL(k_nys_partsum, dim3(1), dim3(256), 0, st, fx_.part, (int64_t)nt * nt, R.rs + 2);
       KCHK();
       sg.end();
     }
-    if (multi_) predict_multi(R, Wt, Av);
   }
-
-  // the cell's nt targets: Kxsx' (nt x n), fs, V' = Kxsx' W' (nt x M), then the
-  // fused covariance kernel on the packed operands (k_nys_cov_mfma)
-  void predict_multi(const CellRefs& R, const double* Wt, const double* Av) {
-    const MultiDev& m = *multi_;
-    const int64_t t0 = m.toffs[R.c], nt = m.toffs[R.c + 1] - t0;
-    if (nt == 0) return;
-    hipStream_t st = st_;
-    const double dn = R.dn, dM = R.dM, dt = (double)nt;
-    const int Tt = (int)blocks(nt, 64), Tkn = (int)blocks(R.n, 64), Tkm = (int)blocks(R.M, 64);
-    sg_.begin(S_PREDM, 2.0 * dt * dn * dM + dt * dt * (dn + dM) + 2.0 * dt * dn,
-              8.0 * (2.0 * dt * dn + 2.0 * dt * dM + dn * dM + (m.cov ? dt * dt : dt)));
-    hipLaunchKernelGGL(k_nys_scale, dim3(blocks(nt, 256)), dim3(256), 0, st, m.xs + t0 * 3, nt, R.hp[0],
-                       R.hp[1], R.hp[2], m.ts, nullptr);
+  if (pred_) {
+    // k* = SGPkernel(x, xs=xs); fs = mean + k*.A; k*'Ki k* = |k*|^2/sn2 - |W k*|^2
+    sg.begin(S_PRED, 2.0 * dn * dM, 8.0 * dn * dM);
+    double* ks = fx_.ks;
+    double* kv = fx_.kv;
+    hipLaunchKernelGGL(k_nys_scale, dim3(1), dim3(64), 0, st, (*tab_)[R.c].xs,
+                       (int64_t)1, R.hp[0], R.hp[1], R.hp[2], fx_.xsc, nullptr);
     KCHK();
-    hipLaunchKernelGGL(k_nys_cross_t, dim3(blocks(nt * R.n, 256)), dim3(256), 0, st, m.ts, nt, R.sc, R.n,
-                       R.hp[3], m.KxT);
+    hipLaunchKernelGGL(k_nys_cross, dim3(blocks(R.n, 256), 1), dim3(256), 0, st, R.sc, nullptr,
+                       R.n, fx_.xsc, nullptr, sf2, ks, R.n);
     KCHK();
-    hipLaunchKernelGGL(k_nys_fs, dim3((unsigned)nt), dim3(256), 0, st, m.KxT, nt, R.n, Av, mean_,
-                       m.fs + t0);
+    hipLaunchKernelGGL(k_nys_dot, dim3(1), dim3(256), 0, st, ks, Av, R.n, R.rs + 7);
     KCHK();
-    oila::gemm(la_, st, false, false,
-               {oila::Gemm{m.KxT, Wt, m.VT, (int)nt, R.iM, R.in, (int)nt, R.in, (int)nt, 1.0, 0.0, 0}});  // V' = Kxsx' W'
-    hipLaunchKernelGGL(k_nys_pack, dim3((unsigned)(Tt * Tkn)), dim3(256), 0, st, m.KxT, nt, R.n, Tt, m.Kp);
+    hipLaunchKernelGGL(k_nys_dot, dim3(1), dim3(256), 0, st, ks, ks, R.n, R.rs + 8);
     KCHK();
-    hipLaunchKernelGGL(k_nys_pack, dim3((unsigned)(Tt * Tkm)), dim3(256), 0, st, m.VT, nt, R.M, Tt, m.Vp);
+    oila::gemv(la_, st, true, {oila::Gemv{Wt, ks, kv, R.in, R.iM, R.in, 1.0, 0.0}});  // kv = W k*
+    hipLaunchKernelGGL(k_nys_dot, dim3(1), dim3(256), 0, st, kv, kv, R.M, R.rs + 9);
     KCHK();
-    double* cov = m.cov ? m.cov + m.coffs[R.c] : nullptr;
-    hipLaunchKernelGGL(k_nys_cov_mfma, dim3((unsigned)(cov ? Tt * (Tt + 1) / 2 : Tt)), dim3(256), 0, st,
-                       m.Kp, (int)blocks(R.n, 16), m.Vp, (int)blocks(R.M, 16), Tt, m.ts, nt, R.hp[3],
-                       R.hp[4], cov, m.var + t0);
-    KCHK();
-    sg_.end();
+    sg.end();
   }
-
-  const std::vector<CellSrc>* tab_;
-  int64_t cap_ = 0;
-  const Knobs kn_;
-  OwnStream own_;  // declared before every buffer: destroyed after them
-  hipStream_t st_;
-  bool obj_ = false, pred_ = false, alloc_obj_, alloc_pred_;
-  DevBuf fixed_, slots_;  // the two workspaces
-  Fixed fx_;              // ... and their arrays
-  Slots sl_;
-  int64_t chunk_ = 1;
-  oila::Stager la_;
-  StageTimer sg_{kStage, S_COUNT};
-  const std::vector<int64_t>* cells_ = nullptr;
-  const double* hyp_ = nullptr;
-  std::vector<int64_t> order_;
-  std::vector<int64_t> cellv_;
-  std::vector<double> hypv_;
-  int64_t ncq_ = 0;
-  double mean_ = 0.0;
-  const MultiDev* multi_ = nullptr;
-  HostBuf hres_, hinfo_;  // pinned: the result copies stay asynchronous
-  double* hr_ = nullptr;
-  int32_t* hi_ = nullptr;
-};
-
-// ---- the steps of one cell's fit (NB1 SMLII + scipy CG), shared by the
-// one-shot fit and the session
-
-// A cell's restated scipy CG at x0 (6-slot; the sixth gradient is 0, which
-// leaves scipy's iteration unchanged) and its first requested point (req, 6).
-// Returns whether the cell wants an evaluation.
-bool cg_start(oi_cg*& cg, const double* x0, double gtol, int32_t maxiter, double* req) {
-  const double x6[6] = {x0[0], x0[1], x0[2], x0[3], x0[4], 0.0};
-  cg = oi_cg_create(x6, gtol, maxiter);
-  if (!cg) throw std::bad_alloc();
-  const int rc = oi_cg_step(cg, req);
-  if (rc < 0) throw HipErr{"oi_cg_step failed"};
-  return rc == 1;
+  if (multi_) predict_multi(R, Wt, Av);
 }
 
-// Feeds one evaluation to the cell's CG; the next requested point into req.
-// Returns whether the cell wants another evaluation.
-bool cg_advance(oi_cg* cg, const CellOut& r, double* req) {
-  const double g6[6] = {r.grad[0], r.grad[1], r.grad[2], r.grad[3], r.grad[4], 0.0};
-  if (oi_cg_feed(cg, r.nlz, g6) != 0) throw HipErr{"oi_cg_feed failed"};
-  const int rc = oi_cg_step(cg, req);
-  if (rc < 0) throw HipErr{"oi_cg_step failed"};
-  return rc == 1;
+// the cell's nt targets: Kxsx' (nt x n), fs, V' = Kxsx' W' (nt x M), then the
+// fused covariance kernel on the packed operands (k_nys_cov_mfma)
+void Runner::predict_multi(const CellRefs& R, const double* Wt, const double* Av) {
+  const MultiDev& m = *multi_;
+  const int64_t t0 = m.toffs[R.c], nt = m.toffs[R.c + 1] - t0;
+  if (nt == 0) return;
+  hipStream_t st = st_;
+  const double dn = R.dn, dM = R.dM, dt = (double)nt;
+  const int Tt = (int)blocks(nt, 64), Tkn = (int)blocks(R.n, 64), Tkm = (int)blocks(R.M, 64);
+  sg_.begin(S_PREDM, 2.0 * dt * dn * dM + dt * dt * (dn + dM) + 2.0 * dt * dn,
+            8.0 * (2.0 * dt * dn + 2.0 * dt * dM + dn * dM + (m.cov ? dt * dt : dt)));
+  hipLaunchKernelGGL(k_nys_scale, dim3(blocks(nt, 256)), dim3(256), 0, st, m.xs + t0 * 3, nt, R.hp[0],
+                     R.hp[1], R.hp[2], m.ts, nullptr);
+  KCHK();
+  hipLaunchKernelGGL(k_nys_cross_t, dim3(blocks(nt * R.n, 256)), dim3(256), 0, st, m.ts, nt, R.sc, R.n,
+                     R.hp[3], m.KxT);
+  KCHK();
+  hipLaunchKernelGGL(k_nys_fs, dim3((unsigned)nt), dim3(256), 0, st, m.KxT, nt, R.n, Av, mean_,
+                     m.fs + t0);
+  KCHK();
+  oila::gemm(la_, st, false, false,
+             {oila::Gemm{m.KxT, Wt, m.VT, (int)nt, R.iM, R.in, (int)nt, R.in, (int)nt, 1.0, 0.0, 0}});  // V' = Kxsx' W'
+  hipLaunchKernelGGL(k_nys_pack, dim3((unsigned)(Tt * Tkn)), dim3(256), 0, st, m.KxT, nt, R.n, Tt, m.Kp);
+  KCHK();
+  hipLaunchKernelGGL(k_nys_pack, dim3((unsigned)(Tt * Tkm)), dim3(256), 0, st, m.VT, nt, R.M, Tt, m.Vp);
+  KCHK();
+  double* cov = m.cov ? m.cov + m.coffs[R.c] : nullptr;
+  hipLaunchKernelGGL(k_nys_cov_mfma, dim3((unsigned)(cov ? Tt * (Tt + 1) / 2 : Tt)), dim3(256), 0, st,
+                     m.Kp, (int)blocks(R.n, 16), m.Vp, (int)blocks(R.M, 16), Tt, m.ts, nt, R.hp[3],
+                     R.hp[4], cov, m.var + t0);
+  KCHK();
+  sg_.end();
 }
 
-// The fitted LINEAR hypers (5) of a finished cell; info[4] = (nit, status,
-// nfev, nobj) when asked for.
-void cg_readout(oi_cg* cg, double* hyp, int32_t* info) {
-  double xf[6], fun;
-  int32_t nit, cst;
-  int64_t nfev, njev, nobj;
-  oi_cg_result(cg, xf, &fun, &nit, &cst, &nfev, &njev, &nobj);
-  if (info) {
-    info[0] = nit;
-    info[1] = cst;
-    info[2] = (int32_t)nfev;
-    info[3] = (int32_t)nobj;
-  }
-  for (int q = 0; q < 5; ++q) hyp[q] = std::exp(xf[q]);
-}
+}  // namespace oi_nys
 
-// out[8] = (fs, sd, prior sd, the 5 fitted hypers): NB1 code cell 5's row
-void write_fit(const CellOut& r, const double* hyp, double* out, int32_t* status) {
-  *status = r.status;
-  out[0] = r.fs;
-  out[1] = r.sd;
-  out[2] = r.sprior;
-  for (int q = 0; q < 5; ++q) out[3 + q] = hyp[q];
-}
-
-}  // namespace
+using namespace oi_nys;
 
 extern "C" int oi_nystrom_batch(const double* xyt, const double* y, const int64_t* offs,
                                 int64_t ncell, const int64_t* sel, const int64_t* soffs,
@@ -1197,7 +891,7 @@ extern "C" int oi_nystrom_batch(const double* xyt, const double* y, const int64_
     BatchDev bd(b, want_pred ? xs : nullptr, o.device_inputs != 0, (hipStream_t)o.stream);
     Runner R(&bd.rows, b.nmax, b.mmax, ncell, o, want_obj, want_pred);
     std::vector<CellOut> out(ncell);
-    R.run_all(ncell, hyp, mean, out.data(), want_obj, want_pred);
+    R.run_all(ncell, hyp, mean, out.data());
     for (int64_t c = 0; c < ncell; ++c) {
       status[c] = out[c].status;
       if (want_obj) {
@@ -1289,7 +983,7 @@ extern "C" int oi_nystrom_predict_multi(const double* xyt, const double* y, cons
     {
       Runner R(&bd.rows, b.nmax, b.mmax, ncell, o, false, false);
       R.set_multi(&md);
-      R.run_all(ncell, hyp, mean, out.data(), false, false);
+      R.run_all(ncell, hyp, mean, out.data());
     }
     // nothing was written so far: every output in one go, once all cells are done
     if (T > 0) {
@@ -1310,313 +1004,4 @@ extern "C" int oi_nystrom_predict_multi(const double* xyt, const double* y, cons
     }
     return 0;
   });
-}
-
-extern "C" int oi_nystrom_fit_batch(const double* xyt, const double* y, const int64_t* offs,
-                                    int64_t ncell, const int64_t* sel, const int64_t* soffs,
-                                    const double* x0, const double* xs, double mean, double* out,
-                                    int32_t* status, int32_t* info, const oi_options* opts) {
-  Batch b{xyt, y, offs, ncell, sel, soffs};
-  if (int rc = check_batch(b)) return rc;
-  if (ncell == 0) return 0;
-  if (!x0 || !xs || !out || !status) return oi_set_last_error(OI_E_ARG, "null pointer");
-  const oi_options o = oi_resolve(opts);
-  if (int rc = oi_select_device(o)) return rc;
-  // scipy: maxiter = len(x0) * 200 for the notebook's 5 hypers
-  const int32_t maxiter = o.maxiter < 0 ? 1000 : o.maxiter;
-  return oi_guarded([&] {
-    // one restated scipy CG per cell, every round one pass over the cells
-    // still iterating
-    std::vector<oi_cg*> cg(ncell, nullptr);
-    struct Free {
-      std::vector<oi_cg*>& v;
-      ~Free() {
-        for (auto* p : v)
-          if (p) oi_cg_destroy(p);
-      }
-    } free_{cg};
-    std::vector<double> req(ncell * 6);
-    std::vector<char> live(ncell, 0);
-    for (int64_t c = 0; c < ncell; ++c) live[c] = cg_start(cg[c], x0, o.gtol, maxiter, req.data() + c * 6);
-    // cells are independent: split them into G groups (OI_NYS_GROUPS, default 2),
-    // each with its own stream, so one group's latency-bound batched
-    // eigh overlaps the other's panels / objective pass; each group is
-    // collected and re-queued as soon as its round is done
-    const int G = (int)std::min<int64_t>(Knobs().groups, ncell);
-    std::vector<std::vector<int64_t>> gcells(G);
-    for (int64_t c = 0; c < ncell; ++c) gcells[c % G].push_back(c);
-    BatchDev bd(b, xs, o.device_inputs != 0, (hipStream_t)o.stream);
-    std::vector<std::unique_ptr<Runner>> RG;
-    for (int g = 0; g < G; ++g)
-      RG.emplace_back(new Runner(&bd.rows, b.nmax, b.mmax, (int64_t)gcells[g].size(), o, true, false, G > 1));
-    std::vector<std::vector<int64_t>> qcells(G);
-    std::vector<CellOut> res(ncell);
-    auto queue = [&](int g) {
-      qcells[g].clear();
-      std::vector<double> hyp;
-      for (int64_t c : gcells[g])
-        if (live[c]) {
-          qcells[g].push_back(c);
-          for (int q = 0; q < 5; ++q) hyp.push_back(std::exp(req[c * 6 + q]));  // NB1 SMLII
-        }
-      if (!qcells[g].empty()) RG[g]->enqueue(qcells[g], hyp.data(), mean, true, false);
-    };
-    for (int g = 0; g < G; ++g) queue(g);
-    for (bool any = true; any;) {
-      any = false;
-      for (int g = 0; g < G; ++g) {
-        if (qcells[g].empty()) continue;
-        any = true;
-        RG[g]->collect(res.data());
-        for (size_t k = 0; k < qcells[g].size(); ++k) {
-          const int64_t c = qcells[g][k];
-          live[c] = cg_advance(cg[c], res[k], req.data() + c * 6);
-        }
-        queue(g);
-      }
-    }
-    RG.clear();
-    Runner R(&bd.rows, b.nmax, b.mmax, ncell, o, false, true);
-    // NB1 code cell 5: GPR(approx=True) at the fitted hypers
-    std::vector<double> hyp(ncell * 5);
-    for (int64_t c = 0; c < ncell; ++c) cg_readout(cg[c], hyp.data() + c * 5, info ? info + c * 4 : nullptr);
-    R.run_all(ncell, hyp.data(), mean, res.data(), false, true);
-    for (int64_t c = 0; c < ncell; ++c) write_fit(res[c], hyp.data() + c * 5, out + c * 8, status + c);
-    return 0;
-  });
-}
-
-// ---- Nystrom fit session: continuous batching across calls (NB1 code cell 5
-// as a stream of batches).  Every submitted batch joins one queue of cells;
-// each of the G groups (own stream, Runner) keeps up to CAP cells fitting and
-// refills from the queue as cells finish, so a call's slowest cells overlap
-// the next calls' cells instead of idling the GPU (the one-shot fit waits for
-// its slowest cell).  A ticket completes when its last cell is fitted; its
-// predictions (GPR(approx=True) at the fitted hypers) run then.  Per-cell
-// arithmetic never depends on the other resident cells, so results equal
-// oi_nystrom_fit_batch's bit for bit.
-namespace {
-struct NysTicket {
-  std::unique_ptr<BatchDev> dev;
-  int64_t first = 0, count = 0, unfitted = 0;
-  double mean = 0.0;
-  double* out = nullptr;
-  int32_t* status = nullptr;
-  int32_t* info = nullptr;
-  bool done = false;
-};
-}  // namespace
-
-struct oi_nystrom_session {
-  oi_options o;
-  const Knobs kn;  // as the environment was at create: kn.groups groups of up to kn.cap fitting cells
-  int32_t maxiter = 1000;
-  double gtol = 1e-5;
-  std::vector<CellSrc> tab;          // every submitted cell, by global id
-  std::vector<int64_t> owner;        // cell -> ticket
-  std::vector<oi_cg*> cg;            // per cell (null before admission / after release)
-  std::vector<double> req;           // per cell: the requested point (6)
-  std::vector<double> x0;            // per cell: the batch's x0 (5)
-  std::deque<int64_t> queue;         // submitted, not admitted
-  std::vector<std::unique_ptr<NysTicket>> tickets;
-  int64_t nmax = 0, mmax = 0;        // the Runners' sizes
-  struct Grp {
-    std::unique_ptr<Runner> R;
-    std::vector<int64_t> active, inflight;
-  };
-  std::vector<Grp> grp;
-  std::unique_ptr<Runner> pred;      // predictions of completed tickets
-  // inputs of submitted batches are allocated, copied and freed on this stream
-  // (stream-ordered): dropping a completed batch never drains the groups'
-  // rounds in flight (a ticket's cells are in no round by then)
-  OwnStream io;
-
-  ~oi_nystrom_session() {
-    for (auto* p : cg)
-      if (p) oi_cg_destroy(p);
-    grp.clear();
-    pred.reset();
-    tickets.clear();
-    if (io.s) (void)hipStreamSynchronize(io.s);
-  }
-
-  void build_runners(int64_t nm, int64_t mm) {
-    nmax = std::max(nmax, nm);
-    mmax = std::max(mmax, mm);
-    grp.resize(kn.groups);
-    for (auto& g : grp) g.R.reset(new Runner(&tab, nmax, mmax, kn.cap, o, true, false, kn.groups > 1));
-    pred.reset(new Runner(&tab, nmax, mmax, kn.cap, o, false, true, true));
-  }
-
-  void feed(Grp& g) {  // collect a group's round, advance its cells' CG
-    if (g.inflight.empty()) return;
-    std::vector<CellOut> res(g.inflight.size());
-    g.R->collect(res.data());
-    for (size_t k = 0; k < g.inflight.size(); ++k) {
-      const int64_t c = g.inflight[k];
-      if (!cg_advance(cg[c], res[k], req.data() + c * 6)) finished(c);
-    }
-    g.inflight.clear();
-    std::vector<int64_t> keep;
-    for (int64_t c : g.active)
-      if (cg[c] && !fitted_[c]) keep.push_back(c);
-    g.active.swap(keep);
-  }
-
-  std::vector<char> fitted_;
-
-  void finished(int64_t c) {
-    fitted_[c] = 1;
-    NysTicket& t = *tickets[owner[c]];
-    if (--t.unfitted == 0) complete(t);
-  }
-
-  void complete(NysTicket& t) {
-    // GPR(approx=True) at the fitted hypers, in chunks of the Runner capacity
-    Runner& R = *pred;
-    const int64_t cap = kn.cap;
-    std::vector<CellOut> res(cap);
-    for (int64_t a = 0; a < t.count; a += cap) {
-      const int64_t b = std::min(t.count, a + cap);
-      std::vector<int64_t> cells(b - a);
-      std::vector<double> hyp((b - a) * 5);
-      for (int64_t k = a; k < b; ++k) {
-        cells[k - a] = t.first + k;
-        cg_readout(cg[t.first + k], hyp.data() + (k - a) * 5, t.info ? t.info + k * 4 : nullptr);
-      }
-      R.run(cells, hyp.data(), t.mean, res.data(), false, true);
-      for (int64_t k = a; k < b; ++k)
-        write_fit(res[k - a], hyp.data() + (k - a) * 5, t.out + k * 8, t.status + k);
-    }
-    for (int64_t k = 0; k < t.count; ++k) {
-      oi_cg_destroy(cg[t.first + k]);
-      cg[t.first + k] = nullptr;
-    }
-    t.done = true;
-    t.dev.reset();  // no round reads the batch any more: freed in io-stream order
-  }
-
-  void admit(Grp& g) {
-    while ((int64_t)g.active.size() < kn.cap && !queue.empty()) {
-      const int64_t c = queue.front();
-      queue.pop_front();
-      if (cg_start(cg[c], x0.data() + c * 5, gtol, maxiter, req.data() + c * 6))
-        g.active.push_back(c);
-      else
-        finished(c);
-    }
-  }
-
-  void launch(Grp& g) {  // one evaluation round of the group's live cells
-    g.inflight.clear();
-    std::vector<double> hyp;
-    for (int64_t c : g.active) {
-      g.inflight.push_back(c);
-      for (int q = 0; q < 5; ++q) hyp.push_back(std::exp(req[c * 6 + q]));  // NB1 SMLII
-    }
-    if (!g.inflight.empty()) g.R->enqueue(g.inflight, hyp.data(), tickets[owner[g.inflight[0]]]->mean, true, false);
-  }
-
-  // rounds until ticket t (all work when t < 0) is complete
-  void wait(int64_t t) {
-    while (true) {
-      if (t >= 0 && tickets[t]->done) return;
-      bool any = false;
-      for (auto& g : grp) {
-        feed(g);
-        admit(g);
-        launch(g);
-        any = any || !g.inflight.empty();
-      }
-      if (!any) {
-        if (t >= 0 && !tickets[t]->done) throw HipErr{"nystrom session: ticket cannot complete"};
-        return;
-      }
-    }
-  }
-
-  // every group idle (their rounds collected and fed), e.g. before the Runners are rebuilt
-  void drain() {
-    for (auto& g : grp) feed(g);
-  }
-};
-
-extern "C" oi_nystrom_session* oi_nystrom_session_create(const oi_options* opts) {
-  const oi_options o = oi_resolve(opts);
-  if (oi_select_device(o)) return nullptr;
-  std::unique_ptr<oi_nystrom_session> s;
-  if (oi_guarded([&] {
-        s = std::make_unique<oi_nystrom_session>();
-        s->o = o;
-        s->io.create();
-        return 0;
-      }))
-    return nullptr;
-  s->maxiter = o.maxiter < 0 ? 1000 : o.maxiter;  // scipy: len(x0) * 200 for NB1's 5 hypers
-  s->gtol = o.gtol;
-  return s.release();
-}
-
-extern "C" int64_t oi_nystrom_session_submit(oi_nystrom_session* s, const double* xyt, const double* y,
-                                             const int64_t* offs, int64_t ncell, const int64_t* sel,
-                                             const int64_t* soffs, const double* x0, const double* xs,
-                                             double mean, double* out, int32_t* status, int32_t* info) {
-  if (!s) return oi_set_last_error(OI_E_ARG, "null session");
-  Batch b{xyt, y, offs, ncell, sel, soffs};
-  if (int rc = check_batch(b)) return rc;
-  if (ncell > 0 && (!x0 || !xs || !out || !status)) return oi_set_last_error(OI_E_ARG, "null pointer");
-  int64_t ticket = -1;
-  const int rc = oi_guarded([&] {
-    HC(hipSetDevice(s->o.device));
-    auto t = std::make_unique<NysTicket>();
-    t->first = (int64_t)s->tab.size();
-    t->count = ncell;
-    t->unfitted = ncell;
-    t->mean = mean;
-    t->out = out;
-    t->status = status;
-    t->info = info;
-    ticket = (int64_t)s->tickets.size();
-    if (ncell > 0) {
-      t->dev.reset(new BatchDev(b, xs, s->o.device_inputs != 0, s->io.s));
-      if (s->grp.empty() || b.nmax > s->nmax || b.mmax > s->mmax) {
-        s->drain();  // no round in flight over the old Runners' workspaces
-        s->build_runners(b.nmax, b.mmax);
-      }
-      for (int64_t c = 0; c < ncell; ++c) {
-        s->tab.push_back(t->dev->rows[c]);
-        s->owner.push_back(ticket);
-        s->cg.push_back(nullptr);
-        s->fitted_.push_back(0);
-        for (int q = 0; q < 6; ++q) s->req.push_back(0.0);
-        for (int q = 0; q < 5; ++q) s->x0.push_back(x0[q]);
-        s->queue.push_back(t->first + c);
-      }
-    } else {
-      t->done = true;
-    }
-    s->tickets.push_back(std::move(t));
-    return 0;
-  });
-  return rc ? rc : ticket;
-}
-
-extern "C" int oi_nystrom_session_wait(oi_nystrom_session* s, int64_t ticket) {
-  if (!s) return oi_set_last_error(OI_E_ARG, "null session");
-  if (ticket >= (int64_t)s->tickets.size()) return oi_set_last_error(OI_E_ARG, "unknown ticket");
-  return oi_guarded([&] {
-    HC(hipSetDevice(s->o.device));
-    s->wait(ticket);
-    return 0;
-  });
-}
-
-extern "C" void oi_nystrom_session_destroy(oi_nystrom_session* s) {
-  if (!s) return;
-  (void)hipSetDevice(s->o.device);
-  try {
-    s->drain();
-  } catch (...) {
-  }
-  delete s;
 }

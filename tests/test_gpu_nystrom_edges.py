@@ -1,5 +1,5 @@
 """Edge shapes, long batches and the fit's grouping of the Nystrom path
-(csrc/oi_nystrom.hip) against the float64 oracle, with the bars of
+(csrc/oi_nystrom.hip, csrc/oi_nystrom_fit.hip) against the float64 oracle, with the bars of
 tests/test_gpu_nystrom.py (tests/nystrom_cases.assert_cell) and bitwise
 equality wherever the same per-cell arithmetic runs in another arrangement.
 
@@ -23,6 +23,9 @@ decision below is one they cannot tell from a wrong one.  What trips where:
   sel not ascending                 test_unsorted_inducing_rows
   predict-only calls                test_objective_only_and_predict_only
   OI_NYS_GROUPS, unequal groups     test_fit_grouping_is_bitwise_neutral
+  OI_NYS_CAP on the one-shot fit    test_cap_knob_leaves_one_shot_fit_alone
+  tickets of unequal means, rounds  test_session_tickets_keep_their_own_mean
+   that hold cells of both
   NaN cell beside healthy cells     test_nan_cell_leaves_mates_unchanged
 
 All inputs come from seeds (tests/nystrom_cases.py); nothing is read from
@@ -264,3 +267,78 @@ def test_fit_matches_scipy_where_decidable(fit_default):
         assert info[k, 0] == r.nit and info[k, 1] == r.status, (c, info[k], r.nit, r.status)
         assert np.all(np.abs(xh[k] - r.x) <= 1e-6 * np.maximum(1.0, np.abs(r.x))), (c, xh[k], r.x)
     assert admitted >= 3, admitted
+
+
+def _nys_launches():
+    k = _lib.profile_json()['kernels']
+    return {n: k[n]['launches'] for n in k if n.startswith('nys_')}
+
+
+def test_cap_knob_leaves_one_shot_fit_alone(monkeypatch):
+    """OI_NYS_CAP sizes a session's groups only: the one-shot fit of the five
+    fit cells with OI_NYS_CAP=1 and without it gives bitwise the same out,
+    status and info, and the same profiled nys_* launch counts (the batched
+    factorisations are launched once per run of equal padded M in a round, so
+    groups of one cell would launch more of them)."""
+    cases = C.screen(C.fit_cases())
+    runs = []
+    for cap in ('1', None):
+        with monkeypatch.context() as m:
+            if cap is None:
+                m.delenv('OI_NYS_CAP', raising=False)
+            else:
+                m.setenv('OI_NYS_CAP', cap)
+            _lib.profile_reset()
+            res = _fit(cases, profile=True)
+            runs.append((res, _nys_launches()))
+    _lib.profile_reset()
+    (capped, lc), (plain, lp) = runs
+    print('nys_* launches:', lp)
+    assert lp and lp.get('nys_grad', 0) > 0, lp
+    for f in range(3):
+        assert same(capped[f], plain[f]), ('OI_NYS_CAP=1', f, capped[f], plain[f])
+    assert lc == lp, (lc, lp)
+
+
+@pytest.mark.parametrize('groups', [None, '1'])
+def test_session_tickets_keep_their_own_mean(groups, monkeypatch):
+    """Two tickets with different prior means, submitted back to back to one
+    session with OI_NYS_CAP=2 before any wait: (40,33), (65,64) at 0.28 and
+    (33,32), (70,31) at -1.5.  Each ticket's rows equal nystrom_fit_batch of
+    its cells at its own mean, bitwise.  With the default two groups each
+    ticket fills one group; with OI_NYS_GROUPS=1 the second ticket's cells are
+    admitted as the first's finish, so rounds hold cells of both tickets: only
+    that case mixes means within a round.  A guard, not a regression test: no
+    objective round has ever read a mean, and now none is given one.
+
+    That the comparison would notice a wrong mean: the first ticket's cells
+    fitted at the other mean differ from it in fs (column 0) in every row, and
+    in nothing else."""
+    shapes = ([(40, 33), (65, 64)], [(33, 32), (70, 31)])
+    means = (0.28, -1.5)
+    for s in shapes[0] + shapes[1]:
+        assert s in C.EDGE_SHAPES
+    tickets = [C.screen([C.Case(n, M, C.H1) for n, M in part]) for part in shapes]
+    monkeypatch.setenv('OI_NYS_CAP', '2')
+    if groups is None:
+        monkeypatch.delenv('OI_NYS_GROUPS', raising=False)
+    else:
+        monkeypatch.setenv('OI_NYS_GROUPS', groups)
+
+    def one_shot(cases, mean):
+        b = C.Batch(cases)
+        return _lib.nystrom_fit_batch(b.xyt, b.y, b.offs, b.sel, b.soffs, C.H1, b.xs, mean, maxiter=C.FIT_MAXITER)
+    ref = [one_shot(cases, mean) for cases, mean in zip(tickets, means)]
+    other = one_shot(tickets[0], means[1])
+    assert np.all(other[0][:, 0] != ref[0][0][:, 0]), (other[0][:, 0], ref[0][0][:, 0])
+    assert np.all(np.abs((ref[0][0][:, 0] - other[0][:, 0]) - (means[0] - means[1])) <= 1e-12)
+    assert same(other[0][:, 1:], ref[0][0][:, 1:]) and same(other[2], ref[0][2])
+    with _lib.NystromSession(maxiter=C.FIT_MAXITER) as s:
+        ids = []
+        for cases, mean in zip(tickets, means):
+            b = C.Batch(cases)
+            ids.append(s.submit(b.xyt, b.y, b.offs, b.sel, b.soffs, C.H1, b.xs, mean))
+        got = [s.wait(t) for t in ids]
+    for j in range(2):
+        for f in range(3):
+            assert same(got[j][f], ref[j][f]), (f"ticket {j} (mean {means[j]})", f, got[j][f], ref[j][f])

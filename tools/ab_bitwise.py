@@ -5,7 +5,9 @@ must not change a single bit).  One small case per entry family:
                 full opt=True fits of a few day cells
   Nystrom       objective + predict, the one-shot fit and a session (two
                 batches) on cells that cross the pad quantum 32 and the 64-tile
-                in n and M
+                in n and M; the one-shot fit in three and in two groups and a
+                session with two cells per group, profiled, on seven unequal
+                cells: their nys_* stage names and launch counts
   prediction    gpr_predict_multi with the covariance, n and nt around the
                 64-tile, in one chunk and in several
   leave-one-out gpr_loo with lpl, n around the 64-tile, in one chunk and in several
@@ -95,11 +97,65 @@ def _nystrom(_lib, synthetic):
             ps, pso = nystrom._ragged_sel(po, Ms[a:b])
             t.append(s.submit(c.xyt[c.offs[a]:c.offs[b]], y[c.offs[a]:c.offs[b]], po, ps, pso, x0, c.xs[a:b], c.mean))
         res = [s.wait(k) for k in t]
-    return dict(nys_nlz=nlz, nys_grad=grad, nys_pred=pred, nys_st=st, nys_stage_names=names,
+    prof = _nystrom_fit_profiled(_lib, synthetic, nystrom)
+    return dict(prof, nys_nlz=nlz, nys_grad=grad, nys_pred=pred, nys_st=st, nys_stage_names=names,
                 nys_stage_launches=launches, nys_fit=fit, nys_fit_st=fst, nys_fit_info=finfo,
                 nys_ses=np.concatenate([r[0] for r in res]), nys_ses_st=np.concatenate([r[1] for r in res]),
                 nys_ses_info=np.concatenate([r[2] for r in res]),
                 nys_dev_fit=dfit[0], nys_dev_fit_st=dfit[1], nys_dev_fit_info=dfit[2])
+
+
+def _nystrom_fit_profiled(_lib, synthetic, nystrom):
+    """The fit's scheduling: results are the same under any grouping of the
+    cells, so what shows that the groups hold the same cells in the same rounds
+    is the nys_* launch counts (the batched factorisations are launched once
+    per run of equal padded M within a round).  Seven unequal cells: a one-shot
+    fit in three groups (3, 2, 2 cells) and the default two, and a session of
+    two tickets whose groups hold two cells each.
+
+    Cells 0..6 have padded M 32, 64, 64, 96, 64, 32, 32.  In three groups cell
+    c belongs to group c mod 3: group 1 is cells {1, 4} (both 64: one batched
+    factorisation per round) and group 2 is cells {2, 5} (64 and 32: two).  A
+    loop that let group 1 take cell 2 from the queue would make them {1, 4, 2}
+    and {5}, one factorisation each, and the counts would show it.  The two
+    knobs are set here and put back as the caller had them."""
+    ns, Ms = [70, 130, 200, 260, 90, 150, 100], np.array([20, 33, 64, 65, 40, 31, 32])
+    c = synthetic.make_cells(ns, seed=6)
+    y = c.z - c.mean
+    sel, soffs = nystrom._ragged_sel(c.offs, Ms)
+    x0 = nystrom.default_x0()
+    r = {}
+
+    knobs = ('OI_NYS_GROUPS', 'OI_NYS_CAP')
+    saved = {k: os.environ[k] for k in knobs if k in os.environ}
+
+    def env(**kw):
+        for k in knobs:
+            os.environ.pop(k, None)
+        os.environ.update(kw)
+    for tag, kw in (('g3', dict(OI_NYS_GROUPS='3')), ('g2', {})):
+        env(**kw)
+        _lib.profile_reset()
+        fit = _lib.nystrom_fit_batch(c.xyt, y, c.offs, sel, soffs, x0, c.xs, c.mean, maxiter=30, profile=True)
+        names, launches = _stages(_lib, 'nys_')
+        r.update({f'nysp_fit_{tag}': fit[0], f'nysp_fit_{tag}_st': fit[1], f'nysp_fit_{tag}_info': fit[2],
+                  f'nysp_fit_{tag}_stage_names': names, f'nysp_fit_{tag}_stage_launches': launches})
+    env(OI_NYS_CAP='2')
+    _lib.profile_reset()
+    with _lib.NystromSession(maxiter=30, profile=True) as s:
+        t = []
+        for a, b in [(0, 4), (4, 7)]:
+            po = c.offs[a:b + 1] - c.offs[a]
+            ps, pso = nystrom._ragged_sel(po, Ms[a:b])
+            t.append(s.submit(c.xyt[c.offs[a]:c.offs[b]], y[c.offs[a]:c.offs[b]], po, ps, pso, x0, c.xs[a:b], c.mean))
+        res = [s.wait(k) for k in t]
+    env(**saved)
+    names, launches = _stages(_lib, 'nys_')
+    _lib.profile_reset()
+    r.update(nysp_ses=np.concatenate([q[0] for q in res]), nysp_ses_st=np.concatenate([q[1] for q in res]),
+             nysp_ses_info=np.concatenate([q[2] for q in res]), nysp_ses_stage_names=names,
+             nysp_ses_stage_launches=launches)
+    return r
 
 
 def _predict(_lib, synthetic):
